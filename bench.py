@@ -19,6 +19,12 @@ all_gather of {id, objective, status, iterations, x*}; a step is one pass over t
 With --gpus N > 1 and no WORLD_SIZE in the environment this process touches neither torch nor HIP:
 it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process and
 exits with its code (never an exec of a process that initialised the GPU).
+
+A plain run sets up, warms up, times the steps and prints the headline line.  `--full` adds what
+takes runs of its own: c4's complete solve checked against lambda_max, the CPU baseline, the
+one-rank RCCL exchange at N = 1, and c5's secondary figures (re-solve, batches in flight, shards
+of 1024).  `--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy
+(float64; the inputs are seeded, so two builds can be compared output for output).
 """
 import argparse
 import json
@@ -310,19 +316,25 @@ def bench_c5(args):
         optimal_all += int(np.sum(rows[:, 2] == 0))
     barrier()
     dt = time.time() - t0
-    # secondary figure: the last batch solved again (twice: the first re-solve already has the order)
-    barrier()
-    t1 = time.time()
-    for _ in range(2):
-        pb.solve_sharded(thetas, device=local)
-    barrier()
-    dt_resolve = (time.time() - t1) / 2.0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"obj_val": rows[:, 1], "status": rows[:, 2], "iterations": rows[:, 3],
+                                         "x": rows[:, 4:]})
+    # the secondary figures below take solves of their own: --full only
+    dt_resolve = None
+    if args.full:
+        # secondary figure: the last batch solved again (twice: the first re-solve already has the order)
+        barrier()
+        t1 = time.time()
+        for _ in range(2):
+            pb.solve_sharded(thetas, device=local)
+        barrier()
+        dt_resolve = (time.time() - t1) / 2.0
     # secondary figure: TWO batches in flight (ParametricBatch.solve_many) — the same fresh batches (first come)
     # through two handles on two streams: the next launch's instances take the compute units the tail of the previous
     # one leaves idle (a launch is as long as its slowest instance; evenly spread the work is ~60 % of it).  What a
     # caller with a stream of batches gets; one batch at a time stays the headline.
     dt_two, n_two = None, 0
-    if world == 1 and args.steps >= 2:
+    if args.full and world == 1 and args.steps >= 2:
         ks = list(range(args.warmup, n_batches))
         pb.solve_many([all_thetas[0], all_thetas[0]], device=local, in_flight=2)      # (the second handle's first call)
         barrier()
@@ -333,7 +345,7 @@ def bench_c5(args):
     # secondary figure: the per-GPU shard BASELINE's config names (8 x 1024) — 1024 fresh instances per launch, all
     # resident at once: the launch is its slowest instance
     dt_1024, it_1024, launch_info, dt_1024_stream = None, None, None, None
-    if world == 1 and B > 1024:
+    if args.full and world == 1 and B > 1024:
         small = [np.stack([sample((n_batches + k) * B + i) for i in range(1024)]) for k in range(4)]
         pb.solve(small[0], device=local)
         barrier()
@@ -352,7 +364,7 @@ def bench_c5(args):
         barrier()
         dt_1024_stream = (time.time() - t4) / len(more)
     launch_info = info.get("launch")                 # the HEADLINE launch's form (the last timed step of this rank)
-    launch_1024 = pb.solve(thetas[: min(B, 1024)], device=local).raw.get("launch") if world == 1 else None
+    launch_1024 = pb.solve(thetas[: min(B, 1024)], device=local).raw.get("launch") if args.full and world == 1 else None
     assert rows.shape[0] == B and np.array_equal(rows[:, 0], np.arange(B)), "gathered rows are not the whole batch"
     gathered_ranks, backend_name = info["ranks"], info["backend"]
     if dist is not None:
@@ -365,7 +377,8 @@ def bench_c5(args):
             backend_name = "nccl (RCCL)"
     else:
         dt_all, ksec_all = dt, ksec
-        r1, b1, backend_name = single_rank_collective(torch, local, rows[0, :4].tolist())
+        if args.full:
+            r1, b1, backend_name = single_rank_collective(torch, local, rows[0, :4].tolist())
     if rank == 0:
         N, m = int(pb.arrays0["dims"][0]), int(pb.arrays0["dims"][1])
         h = pb._handle
@@ -408,7 +421,7 @@ def bench_c5(args):
                        "batch_total": B, "shard": [lo, hi],
                        "optimal": optimal_all // max(args.steps, 1), "acceptable": int(np.sum(rows[:, 2] == 1)),
                        "instance_order": "first come (every step is a fresh batch)",
-                       "resolve_same_batch_problems_per_s": B / dt_resolve if dt_resolve > 0 else None,
+                       "resolve_same_batch_problems_per_s": B / dt_resolve if dt_resolve else None,
                        "two_batches_in_flight_problems_per_s": B * n_two / dt_two if dt_two else None,
                        "shard_of_1024_problems_per_s": 1024 / dt_1024 if dt_1024 else None,
                        "shards_of_1024_four_in_flight_problems_per_s": 1024 / dt_1024_stream if dt_1024_stream else None,
@@ -432,9 +445,9 @@ def bench_c5(args):
                          "note": "one wavefront per instance runs the interior-point loop out of LDS: bound by the instructions it issues and "
                                  "its LDS round trips (`issue`), neither the HBM nor the MFMA roof is near (DESIGN.md 4d / 4e)"},
         }
-        if world > 1 or args.no_cpu:
+        if world > 1 or args.no_cpu or not args.full:
             out["cpu_baseline"] = {"value": None, "unit": "problems/s", "cores": 0, "kind": "port",
-                                   "sample": "not timed (N > 1 or --no-cpu; see the N = 1 line)"}
+                                   "sample": "not timed (N > 1, --no-cpu or no --full; see the N = 1 --full line)"}
         else:
             try:
                 out["cpu_baseline"] = c5_cpu_baseline(args.which, B, (n_batches - 1) * B)
@@ -445,6 +458,28 @@ def bench_c5(args):
     pb.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays {name: array} -> path/<name>.npy in float64.  Above DUMP_MAX_BYTES in all, the arrays with a
+    leading instance axis keep a fixed, seeded sample of their rows (the same rows for every array, listed in
+    sample_rows.npy)."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        rows = max(a.shape[0] for a in arrays.values() if a.ndim)
+        per_row = sum(a.nbytes // rows for a in arrays.values() if a.ndim and a.shape[0] == rows)
+        rest = total - per_row * rows
+        keep = max(1, (DUMP_MAX_BYTES - rest) // (per_row + 8))
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=min(rows, keep), replace=False))
+        arrays = {k: (a[idx] if a.ndim and a.shape[0] == rows else a) for k, a in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def emit(line):
@@ -558,9 +593,14 @@ def main():
     ap.add_argument("--batch", type=int, default=8192, help="c5: instances in the whole job (BASELINE: 8 x 1024)")
     ap.add_argument("--which", default="localization",
                     help="c5 member: localization | circle_packing10 | power_flow | path_planning | circle_packing")
-    ap.add_argument("--cpu-sweep", default="", help="CPU baseline orders as n:iters,... (default: 1000:3,2000:3,4000:2,10000:1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-full-solve", action="store_true", help="c4: skip the complete solve after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: CPU baseline, c4's complete solve, the one-rank RCCL "
+                         "exchange, c5's re-solve / in-flight / 1024-shard figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sweep", default="", help="--full: CPU baseline orders as n:iters,... (default: 1000:3,2000:3,4000:2,10000:1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-full-solve", action="store_true", help="c4 --full without the complete solve after the timed region")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     args = ap.parse_args()
     if args.gpus < 1:
@@ -605,6 +645,8 @@ def main():
     dt = time.time() - t0
     info = h.ipm_finish()
     st1 = h.stats()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: info[k] for k in ("x", "obj_val", "g", "mult_g", "mult_x_L", "mult_x_U")})
     gathered_ranks, gathered_bytes, backend_name = 1, 0, None
     if dist is not None:
         tmax = torch.tensor([dt], device=tdev)
@@ -624,8 +666,9 @@ def main():
             assert backend_name == "nccl (RCCL)", backend_name
     else:
         dt_all = dt
-        gathered_ranks, gathered_bytes, backend_name = single_rank_collective(
-            torch, local, [info["obj_val"], float(info["iterations"]), float(info["status"])])
+        if args.full:
+            gathered_ranks, gathered_bytes, backend_name = single_rank_collective(
+                torch, local, [info["obj_val"], float(info["iterations"]), float(info["status"])])
     if rank == 0:
         # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes of this same
         # command (FETCH_SIZE and WRITE_SIZE cannot share a pass); the committed summary is quoted
@@ -685,7 +728,7 @@ def main():
                          "traffic": traffic, "traffic_unit": "bytes per launch (FETCH x2-corrected + WRITE)",
                          "traffic_source": traffic_src},
         }
-        if not args.no_full_solve:
+        if args.full and not args.no_full_solve:
             # the second half of BASELINE's metric ("solve wall-clock"): ONE complete solve(nlp=True) of the same
             # problem from the same start, after the timed region, checked against lambda_max(A) by power iteration
             # with the device's symmetric product (reference entry point: ipopt_nlpif.py:170, nlp.solve(x0))
@@ -697,6 +740,9 @@ def main():
             # the CPU baseline is a property of the host, not of N: it is timed in the N = 1 run only
             out["cpu_baseline"] = {"value": None, "unit": "iters/s", "cores": 0, "kind": "port",
                                    "sample": "not timed at N > 1 (see the N = 1 line)"}
+        elif not args.full:
+            out["cpu_baseline"] = {"value": None, "unit": "iters/s", "cores": 0, "kind": "port",
+                                   "sample": "not timed (run with --full)"}
         elif not args.no_cpu:
             try:
                 sweep = tuple(tuple(int(v) for v in kv.split(":")) for kv in args.cpu_sweep.split(",")) \

@@ -144,11 +144,11 @@ def test_world_size_1_rccl_gather_on_device(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_c5_one_command_line(tmp_path):
-    """`python bench.py --workload c5` prints one JSON line for the sharded batch with the gather's
+    """`python bench.py --workload c5 --full` prints one JSON line for the sharded batch with the gather's
     evidence (ranks, bytes, backend) and the roofline / cpu_baseline objects."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--batch", "512",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["unit"] == "problems/s" and line["n_gpus"] == 1 and line["value"] > 0

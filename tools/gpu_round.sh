@@ -4,9 +4,9 @@
 #   tools/gpu_round.sh TAG part [part ...]
 # parts
 #   suite      python -m pytest tests -m gpu -q                               -> gpu_suite_tail.txt
-#   bench      python bench.py (the default C4 line) + rocprofv3 kernel table -> bench_n100000.json, bench_n100000_kernel_stats.txt
+#   bench      python bench.py --full (the default C4 line) + rocprofv3 kernel table -> bench_n100000.json, bench_n100000_kernel_stats.txt
 #   pmc_c4     FETCH_SIZE / WRITE_SIZE / MFMA-busy passes of the bench command -> pmc_bench_traffic.json
-#   c5         bench.py --workload c5 at 8192 (with the CPU baseline) and 65536 + kernel table
+#   c5         bench.py --workload c5 --full at 8192 (with the CPU baseline) and 65536 + kernel table
 #   members    the other C5 members at 1024 fresh instances per step          -> c5_members.jsonl
 #   pmc_c5     tools/pmc_c5.sh TAG (counter passes of the C5 bench command)    -> <TAG>_pmc_wave_8192.json
 #   wave       wavefront solver against the generic kernel, every template; phase profile (tools/wave_profile.sh)
@@ -29,7 +29,7 @@ case $PART in
 suite)
   timeout 2400 python -m pytest tests -m gpu -q --timeout=900 > $O/gpu_suite.log 2>&1; tail -4 $O/gpu_suite.log | tee $O/gpu_suite_tail.txt ;;
 bench)
-  ( time timeout 900 python3 bench.py ) > $O/bench_n100000.json 2> $O/bench_default.err; tail -c 2500 $O/bench_n100000.json; tail -4 $O/bench_default.err
+  ( time timeout 900 python3 bench.py --full ) > $O/bench_n100000.json 2> $O/bench_default.err; tail -c 2500 $O/bench_n100000.json; tail -4 $O/bench_default.err
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-full-solve > $O/prof_bench.log 2>&1 < /dev/null
   python3 tools/kstats.py $O/prof_bench > $O/bench_n100000_kernel_stats.txt 2>/dev/null; head -8 $O/bench_n100000_kernel_stats.txt; rm -rf $O/prof_bench ;;
 pmc_c4)
@@ -41,18 +41,18 @@ pmc_c4)
   python3 tools/pmc_c4_post.py $O/pmc_bench_traffic_raw.json $O/pmc_bench_traffic.json 100000 > /dev/null      # (the schema bench.py reads)
   rm -rf $O/bench_FETCH_SIZE $O/bench_WRITE_SIZE $O/bench_SQ_VALU_MFMA_BUSY_CYCLES; head -c 1500 $O/pmc_bench_traffic.json ;;
 c5)
-  timeout 600 python3 bench.py --workload c5 --batch 8192 --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/c5_bench_8192.json; tail -c 2500 $O/c5_bench_8192.json
-  timeout 300 python3 bench.py --workload c5 --batch 65536 --steps 3 --warmup 1 --no-cpu 2>/dev/null | tail -1 > $O/c5_bench_65536.json; tail -c 1200 $O/c5_bench_65536.json
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c5 -- python3 bench.py --workload c5 --batch 8192 --steps 3 --warmup 1 --no-cpu > $O/prof_c5.log 2>&1 < /dev/null
+  timeout 600 python3 bench.py --workload c5 --batch 8192 --steps 5 --warmup 2 --full 2>/dev/null | tail -1 > $O/c5_bench_8192.json; tail -c 2500 $O/c5_bench_8192.json
+  timeout 300 python3 bench.py --workload c5 --batch 65536 --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | tail -1 > $O/c5_bench_65536.json; tail -c 1200 $O/c5_bench_65536.json
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c5 -- python3 bench.py --workload c5 --batch 8192 --steps 3 --warmup 1 --full --no-cpu > $O/prof_c5.log 2>&1 < /dev/null
   python3 tools/kstats.py $O/prof_c5 > $O/c5_kernel_stats.txt 2>/dev/null; head -6 $O/c5_kernel_stats.txt; rm -rf $O/prof_c5 ;;
 members)
   : > $O/c5_members.jsonl
   for W in circle_packing circle_packing10 path_planning power_flow; do
-    timeout 600 python3 bench.py --workload c5 --which $W --batch 1024 --steps 4 --warmup 1 2>/dev/null | grep "^{" | tail -1 >> $O/c5_members.jsonl
+    timeout 600 python3 bench.py --workload c5 --which $W --batch 1024 --steps 4 --warmup 1 --full 2>/dev/null | grep "^{" | tail -1 >> $O/c5_members.jsonl
   done
   # (circle packing n = 10 again at 8192 instances: from 1536 on it runs the workgroup kernel's second form — two wavefronts per
   #  instance, four workgroups per compute unit)
-  timeout 600 python3 bench.py --workload c5 --which circle_packing10 --batch 8192 --steps 3 --warmup 1 --no-cpu 2>/dev/null | grep "^{" | tail -1 >> $O/c5_members.jsonl
+  timeout 600 python3 bench.py --workload c5 --which circle_packing10 --batch 8192 --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | grep "^{" | tail -1 >> $O/c5_members.jsonl
   python3 -c "
 import json
 for l in open('$O/c5_members.jsonl'):
