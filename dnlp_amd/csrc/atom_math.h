@@ -44,10 +44,14 @@ DNLP_HD inline void unary_rules(int op, double u, double p_der, double p_fwd, do
       double lg = log(u);
       val = (u > 0.0) ? -u * lg : (u == 0.0 ? 0.0 : -kInf);
       d1 = -lg - 1.0; d2 = -1.0 / u; break; }
-    case OP_LOGISTIC: {                  // logistic.py:36-39,108-113,97-103
-      double e = exp(u);
-      val = (u > 0.0) ? u + log1p(exp(-u)) : log1p(e);
-      d1 = e / (1.0 + e); d2 = e / ((1.0 + e) * (1.0 + e)); break; }
+    case OP_LOGISTIC: {                  // logistic.py:36-39 (value); the derivatives depart from :108-113,97-103
+      // On purpose not the reference's e / (1 + e) and e / (1 + e)^2 with e = exp(u): e is +inf from u = 709.8 on (both
+      // quotients NaN; the true values are 1 and ~0) and (1 + e)^2 overflows from u ~ 355 on (d2 = 0 where the true value
+      // is a normal number).  Through t = exp(-|u|) <= 1 nothing overflows on either side: sigmoid(u) = 1 / (1 + t) for
+      // u >= 0 and t / (1 + t) for u < 0, and sigmoid(u) sigmoid(-u) = t / (1 + t)^2 for both signs.
+      double t = exp(-fabs(u)), s = 1.0 / (1.0 + t);
+      val = (u > 0.0) ? u + log1p(t) : log1p(t);
+      d1 = (u >= 0.0) ? s : t * s; d2 = t * s * s; break; }
     case OP_POWER: {                     // power.py:187-188,433-450,408-422
       val = pow_fast(u, p_fwd);
       d1 = p_der * pow_fast(u, p_der - 1.0);

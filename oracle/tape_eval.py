@@ -36,8 +36,11 @@ def unary_rules(op, u, p_der, p_fwd):
                            np.where(u == 0, 0.0, -np.inf))
             return val, -np.log(u) - 1.0, -1.0 / u
         if op == OP_LOGISTIC:   # elementwise/logistic.py:36-39,108-113,97-103
-            e = np.exp(u)
-            return np.logaddexp(0, u), e / (1 + e), e / ((1 + e) ** 2)
+            # the derivatives depart from the reference's e / (1 + e), e / (1 + e)^2 on purpose: those are NaN from
+            # u = 709.8 on (e = inf) and d2 is 0 from u ~ 355 on ((1 + e)^2 = inf).  t = exp(-|u|) <= 1 cannot overflow.
+            t = np.exp(-np.abs(u))
+            s = 1.0 / (1.0 + t)
+            return np.logaddexp(0, u), np.where(u >= 0, s, t * s), t * s * s
         if op == OP_POWER:      # elementwise/power.py:187-188 (value), :433-450, :408-422
             return (np.power(u, p_fwd), p_der * np.power(u, p_der - 1),
                     p_der * (p_der - 1) * np.power(u, p_der - 2))
