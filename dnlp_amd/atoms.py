@@ -1071,6 +1071,37 @@ class min(_AxisAtom):  # noqa: A001
         return False
 
 
+class log_sum_exp(_AxisAtom):
+    """log(sum(exp(x))) over all entries or along an axis (reference atoms/log_sum_exp.py:69-103: sign, convex and not
+    concave, ESR and HSR, increasing).  The reference tags it smooth but gives it no derivative rule and no canonical
+    form; here it is a tape op of its own (lowering.py OP_LOG_SUM_EXP)."""
+
+    def numeric(self, values):
+        from scipy.special import logsumexp
+        return logsumexp(_dense(values[0]), axis=self.axis, keepdims=self.keepdims)
+
+    def sign_from_args(self):
+        return (self.args[0].is_nonneg(), False)
+
+    def is_atom_convex(self):
+        return True
+
+    def is_atom_concave(self):
+        return False
+
+    def is_atom_esr(self):
+        return True
+
+    def is_atom_hsr(self):
+        return True
+
+    def is_incr(self, idx):
+        return True
+
+    def is_decr(self, idx):
+        return False
+
+
 class norm1(_AxisAtom):
     """Sum of absolute values (reference atoms/norm1.py): ESR only."""
 

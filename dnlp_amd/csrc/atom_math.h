@@ -11,7 +11,8 @@ enum Op : int {
   OP_EXP = 1, OP_LOG = 2, OP_ENTR = 3, OP_LOGISTIC = 4, OP_POWER = 5, OP_SIN = 6, OP_COS = 7,
   OP_TAN = 8, OP_SINH = 9, OP_TANH = 10, OP_ASINH = 11, OP_ATANH = 12, OP_XEXP = 13,
   OP_MUL = 20, OP_REL_ENTR = 21,
-  OP_QUAD_FORM_DENSE = 30, OP_QUAD_FORM_SPARSE = 31, OP_QUAD_OVER_LIN = 32, OP_MATMUL = 33
+  OP_QUAD_FORM_DENSE = 30, OP_QUAD_FORM_SPARSE = 31, OP_QUAD_OVER_LIN = 32, OP_MATMUL = 33,
+  OP_LOG_SUM_EXP = 34      // row class (model.h sweep_rows): M rows of K entries, one dense K x K Hessian block per row
 };
 
 DNLP_HD inline bool op_is_flat(int op) { return op < OP_QUAD_FORM_DENSE; }

@@ -363,6 +363,7 @@ struct BatchRunner {
   Tape<HipExec>* tape = nullptr;
   SegHost* d_segs = nullptr;
   i64* d_red = nullptr;
+  i64* d_rowsegs = nullptr;   // row-class segment indices (log_sum_exp), as d_red
   SparseConst* d_sparse = nullptr;
   BatchLayout lay;
   i64 in_stride = 0;
@@ -638,6 +639,7 @@ struct BatchRunner {
     for (Buf& b : bufs) if (b.p) hipFree(b.p);
     if (d_segs) hipFree(d_segs);
     if (d_red) hipFree(d_red);
+    if (d_rowsegs) hipFree(d_rowsegs);
     if (d_sparse) hipFree(d_sparse);
     if (d_wave_blk) hipFree(d_wave_blk);
     if (d_wave_blk16) hipFree(d_wave_blk16);
@@ -741,6 +743,7 @@ struct BatchRunner {
     };
     up(&d_segs, t->h_segs.data(), t->h_segs.size());
     up(&d_red, t->h_red_segs.data(), t->h_red_segs.size());
+    up(&d_rowsegs, t->h_row_segs.data(), t->h_row_segs.size());
     up(&d_sparse, t->h_sparse.data(), t->h_sparse.size());
     i64 o = 0;
     auto take = [&](i64& f, i64 n) { f = o; o += n; };
@@ -792,7 +795,7 @@ struct BatchRunner {
     release();
     BatchArgs a;
     a.base = t;           // slice: the view with the shared exec-space index arrays
-    a.base.segs = d_segs; a.base.red_segs = d_red; a.base.sparse = d_sparse;
+    a.base.segs = d_segs; a.base.red_segs = d_red; a.base.row_segs = d_rowsegs; a.base.sparse = d_sparse;
     a.base.dense_ptr = nullptr; a.base.dense_ld = nullptr; a.base.blocks = nullptr;
     a.lay = lay;
     a.batch = batch;

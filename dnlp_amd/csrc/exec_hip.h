@@ -843,6 +843,156 @@ __global__ void __launch_bounds__(kBlock) sweep_flat_kernel(FlatTable t, const d
   }
 }
 
+// ---- tape sweep over the row-class segments (log_sum_exp: hand-written forms of Model::sweep_rows) ----
+// At most three launches per sweep whatever the number of segments and rows: every launch walks a RowTable (tape.h)
+// by its prefix of work.  The order of every sum depends on (K, form) alone: a sweep repeats bit for bit.
+//
+// Short rows (K <= 64): a row is a group of G = next_pow2(K) lanes, 64 / G consecutive rows per wavefront.  max and sum
+// go through an xor butterfly inside the group (every lane ends with the same bits: a + b == b + a), every lane keeps
+// its own p, and the wavefront writes the packed triangles of its rows -- one contiguous run of the Hessian array --
+// with its lanes running linearly over that run (p_i and p_j fetched from the owning lanes).
+__device__ inline void tri_decode(int q, int& i, int& j) {       // q -> (i, j), i >= j, row-major lower triangle; q < 2^23
+  i = static_cast<int>((sqrtf(8.0f * static_cast<float>(q) + 1.0f) - 1.0f) * 0.5f);
+  while (i * (i + 1) / 2 > q) --i;
+  while ((i + 1) * (i + 2) / 2 <= q) ++i;
+  j = q - i * (i + 1) / 2;
+}
+
+__global__ void __launch_bounds__(kBlock) sweep_rows_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                            double* __restrict__ z, double* __restrict__ dv,
+                                                            double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  const int lane = threadIdx.x & 63;
+  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  if (wv >= t.units) return;                         // (a whole wavefront leaves: the shuffles below see 64 lanes)
+  i64 lo = 0, hi = t.n;
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (t.start[mid] <= wv) lo = mid; else hi = mid;
+  }
+  const i64 s = lo;
+  const int K = static_cast<int>(t.K[s]);
+  const i64 M = t.M[s];
+  int G = 1, lg = 0;
+  while (G < K) { G <<= 1; ++lg; }
+  const int per = 64 >> lg;
+  const i64 r0 = (wv - t.start[s]) * per;
+  const int l = lane & (G - 1);
+  const i64 r = r0 + (lane >> lg);
+  const bool valid = r < M && l < K;
+  const i64 e = r * K + l;
+  const i64 a0b = t.a0b[s];
+  double u = -kInf;                                  // padding lanes: exp(-inf - mx) = 0
+  if (valid) u = x[a0b >= 0 ? a0b + e : gidx[t.a0o[s] + e]];
+  double mx = u;
+  for (int d = 1; d < G; d <<= 1) mx = fmax(mx, __shfl_xor(mx, d));
+  const double ev = exp(u - mx);
+  double S = ev;
+  for (int d = 1; d < G; d <<= 1) S += __shfl_xor(S, d);
+  const double p = ev / S;
+  if (valid) {
+    dv[t.doff[s] + e] = p;
+    if (l == 0) z[t.zoff[s] + r] = mx + log(S);
+  }
+  if (!with_h) return;
+  const int T = K * (K + 1) / 2;
+  const i64 left = M - r0;
+  const int tot = static_cast<int>(left < per ? left : per) * T;
+  double* __restrict__ hrun = hv + t.hoff[s] + r0 * T;
+  const double* __restrict__ wrow = ww + t.zoff[s] + r0;
+  for (int q0 = 0; q0 < tot; q0 += 64) {             // (uniform trip count: every lane serves the fetches)
+    const int q = q0 + lane;
+    const bool on = q < tot;
+    const int qq = on ? q : 0;
+    const int row = qq / T;
+    int i, j;
+    tri_decode(qq - row * T, i, j);
+    const double pi = __shfl(p, (row << lg) + i), pj = __shfl(p, (row << lg) + j);
+    if (on) hrun[q] = wrow[row] * (i == j ? pi - pi * pj : -(pi * pj));
+  }
+}
+
+// Long rows (K > 64): one wavefront per row (four rows per workgroup) up to kRowWaveMax entries, one 256-lane workgroup
+// per row beyond.  Lane-strided partial max and sum, the wavefront's fixed DPP tree (wave_ops.h), and for the workgroup
+// form its four wavefront totals combined in one fixed order through LDS.  e_l = exp(u_l - mx) is parked in the row's
+// d slots by the lane that later scales it to p_l.  The Hessian entries are not written here (sweep_rows_hess_kernel).
+__global__ void __launch_bounds__(kBlock) sweep_rows_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                 double* __restrict__ z, double* __restrict__ dv) {
+  static_assert(kBlock == 256, "four wavefronts per workgroup: Tape::load_rows counts four rows per workgroup, and the combines below read sm[0..3]");
+  __shared__ double sm[kBlock / 64];
+  const i64 b = blockIdx.x;
+  i64 lo = 0, hi = t.n;
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (t.start[mid] <= b) lo = mid; else hi = mid;
+  }
+  const i64 s = lo;
+  const i64 K = t.K[s], M = t.M[s];
+  const bool wg = K > kRowWaveMax;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const i64 row = wg ? b - t.start[s] : (b - t.start[s]) * (kBlock / 64) + wid;
+  const bool rowon = row < M;                        // (wavefront-uniform; the reductions below need all 64 lanes)
+  const int W = wg ? kBlock : 64, tid = wg ? static_cast<int>(threadIdx.x) : lane;
+  const i64 a0b = t.a0b[s], base = row * K;
+  const i32* __restrict__ gi = gidx + t.a0o[s] + base;
+  const double* __restrict__ xr = x + (a0b >= 0 ? a0b + base : 0);
+  double* __restrict__ dr = dv + t.doff[s] + base;
+  const i64 Kon = rowon ? K : 0;
+  double mx = -kInf;
+  for (i64 l = tid; l < Kon; l += W) mx = fmax(mx, a0b >= 0 ? xr[l] : x[gi[l]]);
+  mx = wave_all_max(mx);
+  if (wg) {
+    if (lane == 0) sm[wid] = mx;
+    __syncthreads();
+    mx = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
+    __syncthreads();
+  }
+  double S = 0.0;
+  for (i64 l = tid; l < Kon; l += W) {
+    const double ev = exp((a0b >= 0 ? xr[l] : x[gi[l]]) - mx);
+    dr[l] = ev;
+    S += ev;
+  }
+  S = wave_all_sum(S);
+  if (wg) {
+    if (lane == 0) sm[wid] = S;
+    __syncthreads();
+    S = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  }
+  for (i64 l = tid; l < Kon; l += W) dr[l] = dr[l] / S;
+  if (rowon && tid == 0) z[t.zoff[s] + row] = mx + log(S);
+}
+
+// The Hessian entries of all long rows spread over the grid: one entry per lane, consecutive addresses per wavefront,
+// each reading p_i (nearly uniform across a wavefront) and p_j (consecutive) from the d slots the launch before filled.
+__global__ void __launch_bounds__(kBlock) sweep_rows_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
+                                                                 const double* __restrict__ ww) {
+  __shared__ i64 s_first;
+  const i64 e_blk = static_cast<i64>(blockIdx.x) * kBlock;
+  if (threadIdx.x == 0) {
+    i64 lo = 0, hi = t.n;
+    while (hi - lo > 1) {
+      const i64 mid = (lo + hi) >> 1;
+      if (t.hstart[mid] <= e_blk) lo = mid; else hi = mid;
+    }
+    s_first = lo;
+  }
+  __syncthreads();
+  const i64 e = e_blk + threadIdx.x;
+  if (e >= t.hunits) return;
+  i64 s = s_first;
+  while (t.hstart[s + 1] <= e) ++s;
+  const unsigned qa = static_cast<unsigned>(e - t.hstart[s]);       // (a segment's entries fit 31 bits: the lowering's limit)
+  const unsigned K = static_cast<unsigned>(t.K[s]), T = K * (K + 1) / 2;
+  const unsigned row = qa / T, q = qa - row * T;
+  unsigned i = static_cast<unsigned>((sqrt(8.0 * static_cast<double>(q) + 1.0) - 1.0) * 0.5);
+  while (i * (i + 1) / 2 > q) --i;
+  while ((i + 1) * (i + 2) / 2 <= q) ++i;
+  const unsigned j = q - i * (i + 1) / 2;
+  const double* __restrict__ pr = dv + t.doff[s] + static_cast<i64>(row) * K;
+  const double pi = pr[i], pj = pr[j];
+  hv[t.hoff[s] + qa] = ww[t.zoff[s] + row] * (i == j ? pi - pi * pj : -(pi * pj));
+}
+
 // part[q * 1024 + block] = this block's share of sum_i V[q*N + i] * w[i] for q < k (k <= 32): all k dot products in one
 // sweep of w; vt_dot_finish_kernel adds the blocks' shares in block order (round 4: an atomic add per block landed in
 // arrival order — the Lanczos bound of C4 and the host-driven L-BFGS's Gram rows could differ in the last bits)
@@ -1360,6 +1510,19 @@ struct HipExec : HostControlled {
     const i64 grid = (t.total + 2 * kBlock - 1) / (2 * kBlock);
     hipLaunchKernelGGL(sweep_flat_kernel, dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0, stream, t, x, z, dv, hv, w,
                        with_h ? 1 : 0);
+    DNLP_LAUNCH_CHECK();
+  }
+  void sweep_rows(const RowTable& ts, const RowTable& tl, const i32* gidx, const double* x, double* z, double* dv, double* hv,
+                  const double* w, bool with_h) {
+    if (ts.units > 0)
+      hipLaunchKernelGGL(sweep_rows_kernel, dim3(static_cast<unsigned>((ts.units + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
+                         stream, ts, gidx, x, z, dv, hv, w, with_h ? 1 : 0);
+    if (tl.units > 0) {
+      hipLaunchKernelGGL(sweep_rows_long_kernel, dim3(static_cast<unsigned>(tl.units)), dim3(kBlock), 0, stream, tl, gidx, x, z, dv);
+      if (with_h)
+        hipLaunchKernelGGL(sweep_rows_hess_kernel, dim3(static_cast<unsigned>((tl.hunits + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           tl, dv, hv, w);
+    }
     DNLP_LAUNCH_CHECK();
   }
   // Small systems: one workgroup walks all levels (one launch).  Large ones (>= 8192 pivot

@@ -232,6 +232,72 @@ struct Model {
     }
   }
 
+  // row-class segments: log_sum_exp over M rows of K entries (lowering.py _lower_log_sum_exp; the reference's
+  // log_sum_exp.py tags the atom smooth and has no _jacobian / _hess_vec to follow).  Per row, with mx = max_l u_l and
+  // e_l = exp(u_l - mx):
+  //   S = sum_l e_l,  r = mx + log S,  p_l = e_l / S,  h_ij = w_r (delta_ij p_i - p_i p_j)   (lower triangle, row-major)
+  // K = 1 gives r = u, p = 1, h = 0 exactly; a row with +inf or NaN gives NaN (inf - inf).  Three maps -- rows, entries,
+  // Hessian entries -- so that the in-kernel space runs every stage with all its lanes; (mx, S) of a row wait in tmpN
+  // between the first two (rows of K >= 2 distinct entries: 2 M <= N, refused otherwise by Tape::load_rows).  The host-driven device space has kernels of
+  // its own (exec_hip.h sweep_rows_*).
+  DNLP_HD void sweep_rows(const double* x, bool with_h) {
+    DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
+    if (t.nrow == 0) return;
+    if constexpr (E::is_device && E::has_host_control) {
+      ex->sweep_rows(t.row_short, t.row_long, t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
+      return;
+    }
+    for (i64 rk = 0; rk < t.nrow; ++rk) {
+      const SegHost& g = t.segs[t.row_segs[rk]];
+      if (g.op != OP_LOG_SUM_EXP) DNLP_FAIL("row-class segment with an unknown opcode");
+      const i32* gidx = t.gidx;
+      const i64 M = g.d0, K = g.d1, T = K * (K + 1) / 2, a0b = g.a0_base, a0o = g.a0_off;
+      double* z = xz + t.N + g.zoff;
+      double* dv = dvals + g.doff;
+      double* hv = hvals + g.hoff;
+      const double* ww = w + g.zoff;
+      if (K == 1) {
+        // r = u, p = 1, h = 0 exactly for a finite u; through the same expressions as longer rows, so that +-inf and NaN
+        // give NaN here as they do there (exp(u - u)) and in the device kernels
+        ex->map(M, [=] DNLP_HD(i64 r) {
+          const double u = x[a0b >= 0 ? a0b + r : gidx[a0o + r]];
+          const double ev = exp(u - u), p = ev / ev;
+          z[r] = u + log(ev);
+          dv[r] = p;
+          if (with_h) hv[r] = ww[r] * (p - p * p);
+        });
+        continue;
+      }
+      // (2 M <= N for these rows is checked where the tape is loaded: Tape::load_rows)
+      double* ms = tmpN;
+      ex->map(M, [=] DNLP_HD(i64 r) {
+        const i64 b = r * K;
+        double mx = -kInf;
+        for (i64 l = 0; l < K; ++l) { const double u = x[a0b >= 0 ? a0b + b + l : gidx[a0o + b + l]]; if (u > mx) mx = u; }
+        double S = 0.0;
+        for (i64 l = 0; l < K; ++l) S += exp(x[a0b >= 0 ? a0b + b + l : gidx[a0o + b + l]] - mx);
+        z[r] = mx + log(S);
+        ms[2 * r] = mx;
+        ms[2 * r + 1] = S;
+      });
+      ex->map(M * K, [=] DNLP_HD(i64 e) {
+        const i64 r = e / K;
+        dv[e] = exp(x[a0b >= 0 ? a0b + e : gidx[a0o + e]] - ms[2 * r]) / ms[2 * r + 1];
+      });
+      if (!with_h) continue;
+      ex->map(M * T, [=] DNLP_HD(i64 e) {
+        const i64 r = e / T, q = e - r * T;
+        // tril_indices order: row-major over the lower triangle (as hess_coo below)
+        i64 i = static_cast<i64>((sqrt(8.0 * static_cast<double>(q) + 1.0) - 1.0) * 0.5);
+        while (i * (i + 1) / 2 > q) --i;
+        while ((i + 1) * (i + 2) / 2 <= q) ++i;
+        const i64 j = q - i * (i + 1) / 2;
+        const double pi = dv[r * K + i], pj = dv[r * K + j];
+        hv[e] = ww[r] * (i == j ? pi - pi * pj : -(pi * pj));
+      });
+    }
+  }
+
   DNLP_HD void set_x(const double* x) { ex->d2d(xz, x, static_cast<size_t>(t.N) * sizeof(double)); }
 
   // values + first-derivative element arrays at x (x: exec space, N)
@@ -239,6 +305,7 @@ struct Model {
     DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
     set_x(x);
     sweep_flat(xz, with_h);
+    sweep_rows(xz, with_h);
     sweep_reductions(xz, with_h);
   }
 

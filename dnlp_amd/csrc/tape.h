@@ -134,6 +134,20 @@ struct DenseBlock {
 
 struct SparseConst { Csr P, PT; i64 nh = 0; double* hv = nullptr; };
 
+// Row-class segments (OP_LOG_SUM_EXP) as the device sweep walks them (exec_hip.h sweep_rows_*): one table row per
+// segment, exec space.  `start` is the prefix of launch work (wavefronts for the short-row form, workgroups for the
+// long-row forms), `hstart` the prefix of Hessian entries (M K (K + 1) / 2 per segment).
+struct RowTable {
+  i64 n = 0, units = 0, hunits = 0;
+  i64 *start = nullptr, *hstart = nullptr;
+  i64 *K = nullptr, *M = nullptr, *a0b = nullptr, *a0o = nullptr, *zoff = nullptr, *doff = nullptr, *hoff = nullptr;
+};
+// K <= kRowShortMax: a row is a power-of-two group of lanes inside one wavefront.  Above: one wavefront per row up to
+// kRowWaveMax entries (32 serial entries per lane), one 256-lane workgroup per row beyond.  The switch points are recorded
+// with the measured shapes in profiles/log_sum_exp_sweep.jsonl; other values of kRowWaveMax have not been measured.
+constexpr i64 kRowShortMax = 64;
+constexpr i64 kRowWaveMax = 2048;
+
 // Index of a COO pattern BY OUTPUT, built once when the tape is loaded: the entries that feed output g are the
 // segment ptr[g] .. ptr[g+1] of (ent = COO entry, src = index into the multiplied vector), in storage order.
 // A product that walks the segments sums every output in one fixed order: no floating-point atomics, the same
@@ -186,6 +200,9 @@ struct TapeView {
   const SegHost* segs = nullptr;
   const i64* red_segs = nullptr;
   i64 nred = 0;
+  const i64* row_segs = nullptr;        // row-class segments (OP_LOG_SUM_EXP), control space
+  i64 nrow = 0;
+  RowTable row_short, row_long;         // the same segments by kernel form, exec space (device sweep)
   const double** dense_ptr = nullptr;   // per dense constant: exec-space column-major matrix (or null until bound)
   i64* dense_ld = nullptr;
   const SparseConst* sparse = nullptr;
@@ -208,6 +225,7 @@ struct Tape : TapeView {
   std::vector<double> h_x0, h_lb, h_ub, h_cl, h_cu;      // host copies
   std::vector<SegHost> h_segs;
   std::vector<i64> h_red_segs;   // indices of reduction-class segments
+  std::vector<i64> h_row_segs;   // indices of row-class segments
   std::vector<i64> h_flat_seg;   // segment index of every flat-table row
   std::vector<i32> h_jac_rows, h_jac_cols, h_hess_rows, h_hess_cols;
   std::vector<double> h_jac_const;   // |coefficient| of Jacobian entries that are constant (affine rows), else 0
@@ -298,10 +316,13 @@ struct Tape : TapeView {
     std::vector<i64> fs{0}, a0b, a0o, a0l, a1b, a1o, a1l, zo, dof, ho, nn, e0, e1, e2;
     std::vector<i32> fop;
     std::vector<double> fp, fp2;
-    // OP_MATMUL (33) is elementwise-class (one unit per output entry) despite its opcode
+    // OP_MATMUL (33) is elementwise-class (one unit per output entry) despite its opcode; OP_LOG_SUM_EXP (34) is the
+    // row class; 30 .. 32 are the reduction class; anything else is not a tape this library knows
     for (i64 s = 0; s < nseg; ++s) {
       const SegHost& g = h_segs[static_cast<size_t>(s)];
       bool flat = (g.op < 30) || (g.op == 33);
+      if (g.op == 34) { h_row_segs.push_back(s); continue; }
+      if (!flat && !(g.op >= 30 && g.op <= 32)) throw std::runtime_error("tape segment with an unknown opcode: " + std::to_string(g.op));
       if (!flat) { h_red_segs.push_back(s); continue; }
       i64 units = (g.op == 33) ? g.d0 * g.d2 : g.n;
       fs.push_back(fs.back() + units);
@@ -322,6 +343,7 @@ struct Tape : TapeView {
     flat_d0 = up(e0.data(), e0.size()); flat_d1 = up(e1.data(), e1.size()); flat_d2 = up(e2.data(), e2.size());
     flat_p = up(fp.data(), fp.size()); flat_p2 = up(fp2.data(), fp2.size());
     gidx = up(tb.i32s("gidx"), tb.count("gidx"));
+    load_rows();
     c0 = tb.f64("c0")[0];
     c = up(tb.f64("c"), static_cast<size_t>(N + Z));
     b = up(tb.f64("b"), static_cast<size_t>(m));
@@ -406,9 +428,44 @@ struct Tape : TapeView {
     }
     // control-space views of the small host tables
     segs = h_segs.data(); red_segs = h_red_segs.data(); nred = static_cast<i64>(h_red_segs.size());
+    row_segs = h_row_segs.data(); nrow = static_cast<i64>(h_row_segs.size());
     dense_ptr = h_dense_ptr.data(); dense_ld = h_dense_ld.data();
     sparse = h_sparse.data(); blocks = h_blocks.data();
     load_reduction(tb);
+  }
+
+  // the row-class segments split by kernel form, with their prefixes of launch work
+  void load_rows() {
+    for (int form = 0; form < 2; ++form) {
+      std::vector<i64> st{0}, hs{0}, K, M, a0b, a0o, zo, dof, ho;
+      for (i64 s : h_row_segs) {
+        const SegHost& g = h_segs[static_cast<size_t>(s)];
+        const i64 rows = g.d0, len = g.d1;
+        if (rows <= 0 || len <= 0 || g.a0_len != rows * len || g.zcount != rows || g.dcount != rows * len ||
+            g.hcount != rows * (len * (len + 1) / 2))
+          throw std::runtime_error("log_sum_exp segment with inconsistent counts");
+        // the generic sweep parks (max, sum) of every row in an N-vector (model.h sweep_rows): rows that share entries
+        // across rows could outnumber it.  The front-end cannot produce such a tape (the argument is one variable).
+        if (len > 1 && 2 * rows > N) throw std::runtime_error("log_sum_exp segment with more rows than half the variables: its rows share entries");
+        if ((len <= kRowShortMax) != (form == 0)) continue;
+        i64 units;
+        if (form == 0) { i64 grp = 1; while (grp < len) grp <<= 1; const i64 per = 64 / grp; units = (rows + per - 1) / per; }   // wavefronts
+        else units = len <= kRowWaveMax ? (rows + 3) / 4 : rows;                                     // workgroups of four wavefronts
+        st.push_back(st.back() + units);
+        hs.push_back(hs.back() + g.hcount);
+        K.push_back(len); M.push_back(rows); a0b.push_back(g.a0_base); a0o.push_back(g.a0_off);
+        zo.push_back(g.zoff); dof.push_back(g.doff); ho.push_back(g.hoff);
+      }
+      RowTable& rt = form == 0 ? row_short : row_long;
+      rt.n = static_cast<i64>(K.size());
+      rt.units = st.back(); rt.hunits = form == 1 ? hs.back() : 0;
+      if (rt.n == 0) continue;
+      rt.start = up(st.data(), st.size());
+      if (form == 1) rt.hstart = up(hs.data(), hs.size());      // (only the long rows' Hessian launch walks it)
+      rt.K = up(K.data(), K.size()); rt.M = up(M.data(), M.size());
+      rt.a0b = up(a0b.data(), a0b.size()); rt.a0o = up(a0o.data(), a0o.size());
+      rt.zoff = up(zo.data(), zo.size()); rt.doff = up(dof.data(), dof.size()); rt.hoff = up(ho.data(), ho.size());
+    }
   }
 
   void load_reduction(const TapeBlob& tb) {

@@ -112,6 +112,9 @@ ALIAS = {
     # trig_canon.py:37-41, hyperbolic_canon.py:46-50: always a new variable on the open domain
     at.tan: (Aux(lower=-PI_TRUNCATED / 2, upper=PI_TRUNCATED / 2),),
     at.atanh: (Aux(lower=-1, upper=1),),
+    # no reference rule (log_sum_exp.py:85-93 tags the atom smooth, SMOOTH_CANON_METHODS has no entry): the argument
+    # becomes a bare variable, so every row of the atom reads distinct x indices (lowering.py _lower_log_sum_exp)
+    at.log_sum_exp: (PLAIN,),
 }
 
 

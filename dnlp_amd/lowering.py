@@ -45,6 +45,7 @@ OP_EXP, OP_LOG, OP_ENTR, OP_LOGISTIC, OP_POWER = 1, 2, 3, 4, 5
 OP_SIN, OP_COS, OP_TAN, OP_SINH, OP_TANH, OP_ASINH, OP_ATANH, OP_XEXP = 6, 7, 8, 9, 10, 11, 12, 13
 OP_MUL, OP_REL_ENTR = 20, 21
 OP_QUAD_FORM_DENSE, OP_QUAD_FORM_SPARSE, OP_QUAD_OVER_LIN, OP_MATMUL = 30, 31, 32, 33
+OP_LOG_SUM_EXP = 34          # row class: many short (or few long) reductions, one dense Hessian block per row
 
 UNARY_OPS = {
     at.exp: OP_EXP, at.log: OP_LOG, at.entr: OP_ENTR, at.logistic: OP_LOGISTIC,
@@ -297,7 +298,7 @@ class Segment:
     hoff: int = 0
     hcount: int = 0
     aux: int = -1               # constant-matrix id (quad_form) / inner dimension (matmul)
-    dims: tuple = (0, 0, 0)     # matmul (m, k, p)
+    dims: tuple = (0, 0, 0)     # matmul (m, k, p); log_sum_exp (rows M, row length K, 0)
 
 
 @dataclass
@@ -740,6 +741,37 @@ class Lowerer:
                           np.concatenate([a0, a1, np.repeat(a1, n)]),
                           np.repeat(z, 2 * n + 1))
         return self._z_form(seg.zoff, 1)
+
+    def _lower_log_sum_exp(self, e):
+        """Row class (csrc/model.h sweep_rows): M rows of K entries, a0[r*K + l] = x index of entry l of row r.
+        d[r*K + l] = p_l; h = the row's lower triangle in tril_indices order, (i, j) -> w_r (delta_ij p_i - p_i p_j)."""
+        a = e.args[0]
+        g = self._gather(a)
+        if e.axis is None or a.ndim <= 1:
+            M, K, a0 = 1, int(g.size), g
+        else:
+            ax = e.axis if e.axis >= 0 else e.axis + a.ndim
+            if ax == 0:                      # one row per column of the F-ordered argument
+                M, K, a0 = a.shape[1], a.shape[0], g
+            else:                            # one row per matrix row
+                M, K, a0 = a.shape[0], a.shape[1], g.reshape(a.shape, order="F").reshape(-1, order="C")
+        if M * K == 0:
+            raise ValueError("log_sum_exp of an empty argument.")
+        T = K * (K + 1) // 2
+        if self.nh + M * T > 2 ** 31 - 1 or self.nd + M * K > 2 ** 31 - 1:
+            raise ValueError("log_sum_exp: %d row(s) of length %d need %d Hessian entries; the tape's 32-bit index "
+                             "range ends at %d." % (M, K, M * T, 2 ** 31 - 1))
+        rows = a0.reshape(M, K)
+        srt = np.sort(rows, axis=1)
+        if K > 1 and bool(np.any(srt[:, 1:] == srt[:, :-1])):
+            # the packed lower triangle would lose the factor 2 of a repeated index (as OP_MUL refuses a0 == a1)
+            raise ValueError("log_sum_exp: a row reads the same variable entry twice; its argument must have "
+                             "distinct entries (run dnlp2smooth first).")
+        seg = Segment(op=OP_LOG_SUM_EXP, n=M, a0=a0, a1=None, zcount=M, dims=(M, K, 0))
+        z = self.Z + np.arange(M, dtype=np.int64)
+        ii, jj = np.tril_indices(K)
+        self._new_segment(seg, np.repeat(z, K), a0, rows[:, ii].reshape(-1), rows[:, jj].reshape(-1), np.repeat(z, T))
+        return self._z_form(seg.zoff, M)
 
 
 def _is_symmetric(P: np.ndarray) -> bool:
