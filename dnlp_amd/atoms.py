@@ -1102,6 +1102,44 @@ class log_sum_exp(_AxisAtom):
         return False
 
 
+class Prod(_AxisAtom):
+    """Product of entries, over all of them or along an axis (reference atoms/prod.py: sign, neither convex nor concave,
+    increasing on a nonnegative argument).  The reference gives the atom no rule tags, no derivative rule and no canonical
+    form; a product is a polynomial, so it is tagged ESR and HSR here, and it is a tape op of its own (lowering.py
+    OP_PROD)."""
+
+    def numeric(self, values):
+        return np.prod(_dense(values[0]), axis=self.axis, keepdims=self.keepdims)
+
+    def sign_from_args(self):
+        return (self.args[0].is_nonneg(), False)
+
+    def is_atom_convex(self):
+        return False
+
+    def is_atom_concave(self):
+        return False
+
+    def is_atom_esr(self):
+        return True
+
+    def is_atom_hsr(self):
+        return True
+
+    def is_incr(self, idx):
+        return self.args[0].is_nonneg()
+
+    def is_decr(self, idx):
+        return False
+
+
+def prod(expr, axis=None, keepdims=False):
+    """A list means the product of its stacked entries (reference atoms/prod.py:155-156)."""
+    if isinstance(expr, list):
+        return Prod(hstack(expr))
+    return Prod(Expression.cast_to_const(expr), axis, keepdims)
+
+
 class norm1(_AxisAtom):
     """Sum of absolute values (reference atoms/norm1.py): ESR only."""
 

@@ -993,6 +993,197 @@ __global__ void __launch_bounds__(kBlock) sweep_rows_hess_kernel(RowTable t, con
   hv[t.hoff[s] + qa] = ww[t.zoff[s] + row] * (i == j ? pi - pi * pj : -(pi * pj));
 }
 
+// ---- the row class, OP_PROD (hand-written forms of Model::sweep_prod_segment; the rule is stated there) ----
+// The same three launches over row tables of their own (tape.h RowTable: one table per opcode and form), so a sweep of a
+// tape that holds log_sum_exp AND prod rows of both lengths is six launches, each over all segments of its kind; a
+// table with an opcode column would make it three, at the price of one kernel text serving both atoms (the registers of
+// the larger, and log_sum_exp's kernels recompiled).  The order of every product depends on (K, form) alone.
+//
+// The product form of the DPP tree of wave_ops.h (not there: that text also travels into the run-time-compiled kernels).
+// Lanes without a source keep the identity, 1.0; lane 63 ends with the wavefront's product, broadcast through an SGPR.
+__device__ inline double wave_all_prod(double v) {
+  v *= dpp_shift_f64<0x111, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x112, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x114, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x118, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x142, 0xa>(v, 1.0);
+  v *= dpp_shift_f64<0x143, 0xc>(v, 1.0);
+  return wave_lane63(v);
+}
+__device__ inline int wave_all_sum_i32(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
+  return __builtin_amdgcn_readlane(v, 63);
+}
+// what the rule writes where it says 0: a NaN product stays NaN
+__device__ inline double prod_zero(double P0) { return P0 != P0 ? P0 : 0.0; }
+
+// Short rows (K <= 64): groups of G = next_pow2(K) lanes as in sweep_rows_kernel; padding lanes and zero entries carry
+// 1.0 into the xor butterfly of the product (a * b == b * a: every lane of a group ends with the same bits), the zeros
+// are counted beside it.  Every lane keeps its g and u; the wavefront writes the STRICT triangles of its rows as one
+// contiguous run, lanes linear over the run.  g_i and u_j come from the owning lanes; the other four values are fetched
+// only by a wavefront that meets u_j == 0 (wavefront-uniform branch: the fetches need all 64 lanes).
+__global__ void __launch_bounds__(kBlock) sweep_prod_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                            double* __restrict__ z, double* __restrict__ dv,
+                                                            double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  const int lane = threadIdx.x & 63;
+  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  if (wv >= t.units) return;                         // (a whole wavefront leaves: the shuffles below see 64 lanes)
+  i64 lo = 0, hi = t.n;
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (t.start[mid] <= wv) lo = mid; else hi = mid;
+  }
+  const i64 s = lo;
+  const int K = static_cast<int>(t.K[s]);
+  const i64 M = t.M[s];
+  int G = 1, lg = 0;
+  while (G < K) { G <<= 1; ++lg; }
+  const int per = 64 >> lg;
+  const i64 r0 = (wv - t.start[s]) * per;
+  const int l = lane & (G - 1);
+  const i64 r = r0 + (lane >> lg);
+  const bool valid = r < M && l < K;
+  const i64 e = r * K + l;
+  const i64 a0b = t.a0b[s];
+  double u = 1.0;
+  if (valid) u = x[a0b >= 0 ? a0b + e : gidx[t.a0o[s] + e]];
+  const bool zero = u == 0.0;
+  double P0 = zero ? 1.0 : u;
+  int nz = zero ? 1 : 0;
+  for (int d = 1; d < G; d <<= 1) { P0 *= __shfl_xor(P0, d); nz += __shfl_xor(nz, d); }
+  const double g = nz == 0 ? P0 / u : ((nz == 1 && zero) ? P0 : prod_zero(P0));
+  if (valid) {
+    dv[t.doff[s] + e] = g;
+    if (l == 0) z[t.zoff[s] + r] = nz == 0 ? P0 : prod_zero(P0);
+  }
+  if (!with_h || K < 2) return;
+  const int T = K * (K - 1) / 2;
+  const i64 left = M - r0;
+  const int tot = static_cast<int>(left < per ? left : per) * T;
+  double* __restrict__ hrun = hv + t.hoff[s] + r0 * T;
+  const double* __restrict__ wrow = ww + t.zoff[s] + r0;
+  for (int q0 = 0; q0 < tot; q0 += 64) {             // (uniform trip count: every lane serves the fetches)
+    const int q = q0 + lane;
+    const bool on = q < tot;
+    const int qq = on ? q : 0;
+    const int row = qq / T;
+    int i, j;
+    tri_decode(qq - row * T, i, j);                  // (entry q of the strict triangle = entry q of the full one, a row down)
+    ++i;
+    const int li = (row << lg) + i, lj = (row << lg) + j;
+    const double gi = __shfl(g, li), uj = __shfl(u, lj);
+    double h = gi / (uj == 0.0 ? 1.0 : uj);          // (no division by zero, not even in a value that is replaced below)
+    if (__any(on && uj == 0.0)) {
+      const double gj = __shfl(g, lj), ui = __shfl(u, li), Pr = __shfl(P0, li);
+      const int nr = __shfl(nz, li);
+      if (uj == 0.0) h = ui != 0.0 ? gj / ui : (nr == 2 ? Pr : prod_zero(Pr));
+    }
+    if (on) hrun[q] = wrow[row] * h;
+  }
+}
+
+// Long rows (K > 64): one wavefront per row (four rows per workgroup) up to kRowWaveMax entries, one 256-lane workgroup
+// per row beyond, as sweep_rows_long_kernel.  Lane-strided partial products and zero counts, the DPP tree above, and for
+// the workgroup form the four wavefront totals combined in one fixed order through LDS.  g needs u once more (re-read:
+// nothing is parked in the d slots).  With the Hessian on, two things wait in the table's park array for the next launch:
+// what it cannot rebuild from g and u -- the entry of two zero positions, nz == 2 ? P0 : Z0, one double per row -- and a
+// contiguous copy of the row (an axis-1 row of an F-ordered argument lies strided in x, and the Hessian launch reads u_j
+// with consecutive j in consecutive lanes).
+__global__ void __launch_bounds__(kBlock) sweep_prod_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                 double* __restrict__ z, double* __restrict__ dv, int with_h) {
+  static_assert(kBlock == 256, "four wavefronts per workgroup: Tape::load_rows counts four rows per workgroup, and the combines below read sm[0..3]");
+  __shared__ double sm[kBlock / 64];
+  __shared__ int sn[kBlock / 64];
+  const i64 b = blockIdx.x;
+  i64 lo = 0, hi = t.n;
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (t.start[mid] <= b) lo = mid; else hi = mid;
+  }
+  const i64 s = lo;
+  const i64 K = t.K[s], M = t.M[s];
+  const bool wg = K > kRowWaveMax;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const i64 row = wg ? b - t.start[s] : (b - t.start[s]) * (kBlock / 64) + wid;
+  const bool rowon = row < M;                        // (wavefront-uniform; the reductions below need all 64 lanes)
+  const int W = wg ? kBlock : 64, tid = wg ? static_cast<int>(threadIdx.x) : lane;
+  const i64 a0b = t.a0b[s], base = row * K;
+  const i32* __restrict__ gi = gidx + t.a0o[s] + base;
+  const double* __restrict__ xr = x + (a0b >= 0 ? a0b + base : 0);
+  double* __restrict__ dr = dv + t.doff[s] + base;
+  const i64 Kon = rowon ? K : 0;
+  double P0 = 1.0;
+  int nz = 0;
+  for (i64 l = tid; l < Kon; l += W) {
+    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
+    if (u == 0.0) ++nz; else P0 *= u;
+  }
+  P0 = wave_all_prod(P0);
+  nz = wave_all_sum_i32(nz);
+  if (wg) {
+    if (lane == 0) { sm[wid] = P0; sn[wid] = nz; }
+    __syncthreads();
+    P0 = (sm[0] * sm[1]) * (sm[2] * sm[3]);
+    nz = (sn[0] + sn[1]) + (sn[2] + sn[3]);
+  }
+  const double Z0 = prod_zero(P0);
+  double* __restrict__ ur = t.park + 4 * t.units + t.ustart[s] + base;
+  for (i64 l = tid; l < Kon; l += W) {
+    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
+    dr[l] = nz == 0 ? P0 / u : ((nz == 1 && u == 0.0) ? P0 : Z0);
+    if (with_h) ur[l] = u;
+  }
+  if (rowon && tid == 0) {
+    z[t.zoff[s] + row] = nz == 0 ? P0 : Z0;
+    if (with_h) t.park[4 * t.start[s] + row] = nz == 2 ? P0 : Z0;
+  }
+}
+
+// The strict-triangle entries of all long rows spread over the grid as in sweep_rows_hess_kernel: one entry per lane,
+// g from the d slots and u from the copy the launch before filled.
+__global__ void __launch_bounds__(kBlock) sweep_prod_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
+                                                                 const double* __restrict__ ww) {
+  __shared__ i64 s_first;
+  const i64 e_blk = static_cast<i64>(blockIdx.x) * kBlock;
+  if (threadIdx.x == 0) {
+    i64 lo = 0, hi = t.n;
+    while (hi - lo > 1) {
+      const i64 mid = (lo + hi) >> 1;
+      if (t.hstart[mid] <= e_blk) lo = mid; else hi = mid;
+    }
+    s_first = lo;
+  }
+  __syncthreads();
+  const i64 e = e_blk + threadIdx.x;
+  if (e >= t.hunits) return;
+  i64 s = s_first;
+  while (t.hstart[s + 1] <= e) ++s;
+  const unsigned qa = static_cast<unsigned>(e - t.hstart[s]);       // (a segment's entries fit 31 bits: the lowering's limit)
+  const unsigned K = static_cast<unsigned>(t.K[s]), T = K * (K - 1) / 2;
+  const unsigned row = qa / T, q = qa - row * T;
+  unsigned i = static_cast<unsigned>((sqrt(8.0 * static_cast<double>(q) + 1.0) - 1.0) * 0.5);
+  while (i * (i + 1) / 2 > q) --i;
+  while ((i + 1) * (i + 2) / 2 <= q) ++i;
+  const unsigned j = q - i * (i + 1) / 2;
+  ++i;
+  const i64 base = static_cast<i64>(row) * K;
+  const double* __restrict__ gr = dv + t.doff[s] + base;
+  const double* __restrict__ ur = t.park + 4 * t.units + t.ustart[s] + base;
+  const double uj = ur[j];
+  double h;
+  if (uj != 0.0) h = gr[i] / uj;
+  else {
+    const double ui = ur[i];
+    h = ui != 0.0 ? gr[j] / ui : t.park[4 * t.start[s] + row];
+  }
+  hv[t.hoff[s] + qa] = ww[t.zoff[s] + row] * h;
+}
+
 // part[q * 1024 + block] = this block's share of sum_i V[q*N + i] * w[i] for q < k (k <= 32): all k dot products in one
 // sweep of w; vt_dot_finish_kernel adds the blocks' shares in block order (round 4: an atomic add per block landed in
 // arrival order — the Lanczos bound of C4 and the host-driven L-BFGS's Gram rows could differ in the last bits)
@@ -1524,6 +1715,20 @@ struct HipExec : HostControlled {
                            tl, dv, hv, w);
     }
     DNLP_LAUNCH_CHECK();
+  }
+  void sweep_prod(const RowTable& ts, const RowTable& tl, const i32* gidx, const double* x, double* z, double* dv, double* hv,
+                  const double* w, bool with_h) {
+    if (ts.units > 0)
+      hipLaunchKernelGGL(sweep_prod_kernel, dim3(static_cast<unsigned>((ts.units + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
+                         stream, ts, gidx, x, z, dv, hv, w, with_h ? 1 : 0);
+    if (tl.units > 0) {
+      hipLaunchKernelGGL(sweep_prod_long_kernel, dim3(static_cast<unsigned>(tl.units)), dim3(kBlock), 0, stream, tl, gidx, x, z, dv,
+                         with_h ? 1 : 0);
+      if (with_h)
+        hipLaunchKernelGGL(sweep_prod_hess_kernel, dim3(static_cast<unsigned>((tl.hunits + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           tl, dv, hv, w);
+    }
+    if (ts.units > 0 || tl.units > 0) DNLP_LAUNCH_CHECK();
   }
   // Small systems: one workgroup walks all levels (one launch).  Large ones (>= 8192 pivot
   // blocks): one grid-wide kernel per level phase, sized by that level's blocks / rows / triples.

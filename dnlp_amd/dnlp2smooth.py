@@ -115,6 +115,8 @@ ALIAS = {
     # no reference rule (log_sum_exp.py:85-93 tags the atom smooth, SMOOTH_CANON_METHODS has no entry): the argument
     # becomes a bare variable, so every row of the atom reads distinct x indices (lowering.py _lower_log_sum_exp)
     at.log_sum_exp: (PLAIN,),
+    # no reference rule either (prod.py has no rule tags): the same alias, and no bounds -- a product has no domain
+    at.Prod: (PLAIN,),
 }
 
 

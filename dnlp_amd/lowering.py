@@ -46,6 +46,7 @@ OP_SIN, OP_COS, OP_TAN, OP_SINH, OP_TANH, OP_ASINH, OP_ATANH, OP_XEXP = 6, 7, 8,
 OP_MUL, OP_REL_ENTR = 20, 21
 OP_QUAD_FORM_DENSE, OP_QUAD_FORM_SPARSE, OP_QUAD_OVER_LIN, OP_MATMUL = 30, 31, 32, 33
 OP_LOG_SUM_EXP = 34          # row class: many short (or few long) reductions, one dense Hessian block per row
+OP_PROD = 35                 # row class: the same rows with the STRICT lower triangle (a product's Hessian diagonal is zero)
 
 UNARY_OPS = {
     at.exp: OP_EXP, at.log: OP_LOG, at.entr: OP_ENTR, at.logistic: OP_LOGISTIC,
@@ -298,7 +299,7 @@ class Segment:
     hoff: int = 0
     hcount: int = 0
     aux: int = -1               # constant-matrix id (quad_form) / inner dimension (matmul)
-    dims: tuple = (0, 0, 0)     # matmul (m, k, p); log_sum_exp (rows M, row length K, 0)
+    dims: tuple = (0, 0, 0)     # matmul (m, k, p); log_sum_exp / prod (rows M, row length K, 0)
 
 
 @dataclass
@@ -742,9 +743,10 @@ class Lowerer:
                           np.repeat(z, 2 * n + 1))
         return self._z_form(seg.zoff, 1)
 
-    def _lower_log_sum_exp(self, e):
-        """Row class (csrc/model.h sweep_rows): M rows of K entries, a0[r*K + l] = x index of entry l of row r.
-        d[r*K + l] = p_l; h = the row's lower triangle in tril_indices order, (i, j) -> w_r (delta_ij p_i - p_i p_j)."""
+    def _row_class(self, e, name, op, diag):
+        """Row class (csrc/model.h sweep_rows): M rows of K entries, a0[r*K + l] = x index of entry l of row r, one z per
+        row, d[r*K + l] = the row's derivative by entry l, h = the row's lower triangle in tril_indices order, with the
+        diagonal (`diag` = 0) or without it (`diag` = -1)."""
         a = e.args[0]
         g = self._gather(a)
         if e.axis is None or a.ndim <= 1:
@@ -756,22 +758,31 @@ class Lowerer:
             else:                            # one row per matrix row
                 M, K, a0 = a.shape[0], a.shape[1], g.reshape(a.shape, order="F").reshape(-1, order="C")
         if M * K == 0:
-            raise ValueError("log_sum_exp of an empty argument.")
-        T = K * (K + 1) // 2
+            raise ValueError("%s of an empty argument." % name)
+        T = K * (K + 1) // 2 if diag == 0 else K * (K - 1) // 2
         if self.nh + M * T > 2 ** 31 - 1 or self.nd + M * K > 2 ** 31 - 1:
-            raise ValueError("log_sum_exp: %d row(s) of length %d need %d Hessian entries; the tape's 32-bit index "
-                             "range ends at %d." % (M, K, M * T, 2 ** 31 - 1))
+            raise ValueError("%s: %d row(s) of length %d need %d Hessian entries; the tape's 32-bit index "
+                             "range ends at %d." % (name, M, K, M * T, 2 ** 31 - 1))
         rows = a0.reshape(M, K)
         srt = np.sort(rows, axis=1)
         if K > 1 and bool(np.any(srt[:, 1:] == srt[:, :-1])):
             # the packed lower triangle would lose the factor 2 of a repeated index (as OP_MUL refuses a0 == a1)
-            raise ValueError("log_sum_exp: a row reads the same variable entry twice; its argument must have "
-                             "distinct entries (run dnlp2smooth first).")
-        seg = Segment(op=OP_LOG_SUM_EXP, n=M, a0=a0, a1=None, zcount=M, dims=(M, K, 0))
+            raise ValueError("%s: a row reads the same variable entry twice; its argument must have "
+                             "distinct entries (run dnlp2smooth first)." % name)
+        seg = Segment(op=op, n=M, a0=a0, a1=None, zcount=M, dims=(M, K, 0))
         z = self.Z + np.arange(M, dtype=np.int64)
-        ii, jj = np.tril_indices(K)
+        ii, jj = np.tril_indices(K, diag)
         self._new_segment(seg, np.repeat(z, K), a0, rows[:, ii].reshape(-1), rows[:, jj].reshape(-1), np.repeat(z, T))
         return self._z_form(seg.zoff, M)
+
+    def _lower_log_sum_exp(self, e):
+        """d[r*K + l] = p_l; h: the lower triangle with its diagonal, (i, j) -> w_r (delta_ij p_i - p_i p_j)."""
+        return self._row_class(e, "log_sum_exp", OP_LOG_SUM_EXP, 0)
+
+    def _lower_Prod(self, e):
+        """d[r*K + l] = prod_{k != l} u_k; h: the STRICT lower triangle, (i, j) -> w_r prod_{k != i, j} u_k.  K = 1: no
+        Hessian entry, d = 1, z = u."""
+        return self._row_class(e, "prod", OP_PROD, -1)
 
 
 def _is_symmetric(P: np.ndarray) -> bool:
