@@ -1192,7 +1192,9 @@ class norm_inf(_AxisAtom):
 
 class Pnorm(_AxisAtom):
     """Vector p-norm, p not in {1, inf} (reference atoms/pnorm.py:50-300).
-    Only p=2 has a dnlp2smooth rule (pnorm_canon.py:29-34)."""
+    Only p=2 has a dnlp2smooth rule (pnorm_canon.py:29-34).  A scalar-valued 2-norm goes through quad_over_lin as in the
+    reference; one taken along an axis (a vector of norms, which the reference's rule cannot canonicalise) goes through
+    QuadOverLinRows, one row per norm."""
 
     def __init__(self, x, p=2, axis=None, keepdims=False, max_denom=1024):
         self.p = p
@@ -1437,6 +1439,52 @@ class quad_over_lin(Atom):
 
     def is_decr(self, idx):
         return (idx == 0 and self.args[0].is_nonpos()) or idx == 1
+
+
+class QuadOverLinRows(Atom, _AxisMixin):
+    """sum(X^2, axis) / y, one entry per row: quad_over_lin applied to every row of X with a denominator of its own
+    (the reference's quad_over_lin.py has no axis; its pnorm_canon.py:22-34 therefore cannot canonicalise a norm along an
+    axis).  `y` has the atom's own shape.  Sign, curvature, rule tags and monotonicity are quad_over_lin's, per row; it is
+    a tape op of its own (lowering.py OP_QUAD_OVER_LIN_ROWS)."""
+
+    def __init__(self, X, y, axis=None, keepdims=False):
+        self.axis = axis
+        self.keepdims = keepdims
+        super().__init__(X, y)
+
+    def get_data(self):
+        return [self.axis, self.keepdims]
+
+    def validate_arguments(self):
+        if self.args[1].shape != self._axis_shape():
+            raise ValueError("The second argument to quad_over_lin_rows must have the shape of the result, %s (got %s)."
+                             % (self._axis_shape(), self.args[1].shape))
+
+    def shape_from_args(self):
+        return self._axis_shape()
+
+    def numeric(self, values):
+        ss = np.square(_dense(values[0])).sum(axis=self.axis, keepdims=self.keepdims)
+        return ss / np.asarray(values[1], dtype=float).reshape(np.shape(ss), order="F")
+
+    def sign_from_args(self):
+        return (True, False)
+
+    def is_atom_convex(self):
+        return True
+
+    def is_atom_concave(self):
+        return False
+
+    def is_incr(self, idx):
+        return idx == 0 and self.args[0].is_nonneg()
+
+    def is_decr(self, idx):
+        return (idx == 0 and self.args[0].is_nonpos()) or idx == 1
+
+
+def quad_over_lin_rows(X, y, axis=None, keepdims=False):
+    return QuadOverLinRows(X, y, axis, keepdims)
 
 
 def sum_squares(expr):

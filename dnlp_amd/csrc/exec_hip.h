@@ -1184,6 +1184,119 @@ __global__ void __launch_bounds__(kBlock) sweep_prod_hess_kernel(RowTable t, con
   hv[t.hoff[s] + qa] = ww[t.zoff[s] + row] * h;
 }
 
+// ---- the row class, OP_QUAD_OVER_LIN_ROWS (hand-written forms of Model::sweep_qol_rows_segment; the rule is stated there) ----
+// Two tables of their own (tape.h RowTable, with the a1 columns), two kernels, at most two launches per sweep for all
+// segments of the op: a row's Hessian is an arrow of 2K + 1 entries, written by the lanes that hold u_l, so there is no
+// third launch and no packed-index decode.  No floating-point atomics; the order of ss depends on (K, form) alone.
+//
+// Short rows (K <= 64): groups of G = next_pow2(K) lanes as in sweep_rows_kernel (K = 2, 3: 32 and 16 rows per
+// wavefront).  u^2 goes through the xor butterfly inside the group, padding lanes carry 0 (a + b == b + a: every lane of
+// a group ends with the same bits).  Every lane of a group reads the group's y and w (one address per group: the
+// hardware merges them) and writes its g_l, h_ll, h_ly at r K + l -- across the wavefront consecutive addresses in each
+// of the three blocks; lane 0 of the group writes z, g_y, h_yy.  No LDS.
+__global__ void __launch_bounds__(kBlock) sweep_qol_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                           double* __restrict__ z, double* __restrict__ dv,
+                                                           double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  const int lane = threadIdx.x & 63;
+  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  if (wv >= t.units) return;                         // (a whole wavefront leaves: the shuffles below see 64 lanes)
+  i64 lo = 0, hi = t.n;
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (t.start[mid] <= wv) lo = mid; else hi = mid;
+  }
+  const i64 s = lo;
+  const int K = static_cast<int>(t.K[s]);
+  const i64 M = t.M[s];
+  int G = 1, lg = 0;
+  while (G < K) { G <<= 1; ++lg; }
+  const int per = 64 >> lg;
+  const i64 r0 = (wv - t.start[s]) * per;
+  const int l = lane & (G - 1);
+  const i64 r = r0 + (lane >> lg);
+  const bool valid = r < M && l < K;
+  const i64 e = r * K + l;
+  const i64 a0b = t.a0b[s];
+  double u = 0.0;
+  if (valid) u = x[a0b >= 0 ? a0b + e : gidx[t.a0o[s] + e]];
+  double ss = u * u;
+  for (int d = 1; d < G; d <<= 1) ss += __shfl_xor(ss, d);
+  if (!valid) return;                                // (no exchange between lanes from here on)
+  const i64 a1b = t.a1b[s], MK = M * K;
+  const double y = x[a1b >= 0 ? a1b + r : gidx[t.a1o[s] + r]];
+  double* __restrict__ ds = dv + t.doff[s];
+  ds[e] = 2.0 * u / y;
+  if (l == 0) {
+    z[t.zoff[s] + r] = ss / y;
+    ds[MK + r] = -ss / (y * y);
+  }
+  if (!with_h) return;
+  const double w = ww[t.zoff[s] + r];
+  double* __restrict__ hs = hv + t.hoff[s];
+  hs[e] = 2.0 * w / y;
+  hs[MK + M + e] = -2.0 * w * u / (y * y);
+  if (l == 0) hs[MK + r] = 2.0 * w * ss / (y * y * y);
+}
+
+// Long rows (K > 64): one wavefront per row (four rows per workgroup) up to kRowWaveMax entries, one 256-lane workgroup
+// per row beyond, as sweep_rows_long_kernel.  Lane-strided partial sums of u^2, the fixed DPP tree (wave_ops.h), and for
+// the workgroup form the four wavefront totals combined in one order through LDS; then a second lane-strided pass over
+// the row (u re-read: a row of 8 K bytes that the first pass has just brought in) writes g and both Hessian blocks.
+__global__ void __launch_bounds__(kBlock) sweep_qol_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                double* __restrict__ z, double* __restrict__ dv,
+                                                                double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  static_assert(kBlock == 256, "four wavefronts per workgroup: Tape::load_rows counts four rows per workgroup, and the combine below reads sm[0..3]");
+  __shared__ double sm[kBlock / 64];
+  const i64 b = blockIdx.x;
+  i64 lo = 0, hi = t.n;
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (t.start[mid] <= b) lo = mid; else hi = mid;
+  }
+  const i64 s = lo;
+  const i64 K = t.K[s], M = t.M[s];
+  const bool wg = K > kRowWaveMax;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const i64 row = wg ? b - t.start[s] : (b - t.start[s]) * (kBlock / 64) + wid;
+  const bool rowon = row < M;                        // (wavefront-uniform; the reduction below needs all 64 lanes)
+  const int W = wg ? kBlock : 64, tid = wg ? static_cast<int>(threadIdx.x) : lane;
+  const i64 a0b = t.a0b[s], base = row * K;
+  const i32* __restrict__ gi = gidx + t.a0o[s] + base;
+  const double* __restrict__ xr = x + (a0b >= 0 ? a0b + base : 0);
+  const i64 Kon = rowon ? K : 0;
+  double ss = 0.0;
+  for (i64 l = tid; l < Kon; l += W) {
+    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
+    ss += u * u;
+  }
+  ss = wave_all_sum(ss);
+  if (wg) {                                          // (uniform over the workgroup: every wavefront meets the barrier)
+    if (lane == 0) sm[wid] = ss;
+    __syncthreads();
+    ss = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  }
+  if (!rowon) return;
+  const i64 a1b = t.a1b[s], MK = M * K;
+  const double y = x[a1b >= 0 ? a1b + row : gidx[t.a1o[s] + row]];
+  const double w = with_h ? ww[t.zoff[s] + row] : 0.0;
+  double* __restrict__ dr = dv + t.doff[s] + base;
+  double* __restrict__ hd = hv + t.hoff[s] + base;
+  double* __restrict__ hc = hv + t.hoff[s] + MK + M + base;
+  for (i64 l = tid; l < K; l += W) {
+    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
+    dr[l] = 2.0 * u / y;
+    if (with_h) {
+      hd[l] = 2.0 * w / y;
+      hc[l] = -2.0 * w * u / (y * y);
+    }
+  }
+  if (tid == 0) {
+    z[t.zoff[s] + row] = ss / y;
+    dv[t.doff[s] + MK + row] = -ss / (y * y);
+    if (with_h) hv[t.hoff[s] + MK + row] = 2.0 * w * ss / (y * y * y);
+  }
+}
+
 // part[q * 1024 + block] = this block's share of sum_i V[q*N + i] * w[i] for q < k (k <= 32): all k dot products in one
 // sweep of w; vt_dot_finish_kernel adds the blocks' shares in block order (round 4: an atomic add per block landed in
 // arrival order — the Lanczos bound of C4 and the host-driven L-BFGS's Gram rows could differ in the last bits)
@@ -1728,6 +1841,16 @@ struct HipExec : HostControlled {
         hipLaunchKernelGGL(sweep_prod_hess_kernel, dim3(static_cast<unsigned>((tl.hunits + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
                            tl, dv, hv, w);
     }
+    if (ts.units > 0 || tl.units > 0) DNLP_LAUNCH_CHECK();
+  }
+  void sweep_qol(const RowTable& ts, const RowTable& tl, const i32* gidx, const double* x, double* z, double* dv, double* hv,
+                 const double* w, bool with_h) {
+    if (ts.units > 0)
+      hipLaunchKernelGGL(sweep_qol_kernel, dim3(static_cast<unsigned>((ts.units + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
+                         stream, ts, gidx, x, z, dv, hv, w, with_h ? 1 : 0);
+    if (tl.units > 0)
+      hipLaunchKernelGGL(sweep_qol_long_kernel, dim3(static_cast<unsigned>(tl.units)), dim3(kBlock), 0, stream, tl, gidx, x, z, dv, hv, w,
+                         with_h ? 1 : 0);
     if (ts.units > 0 || tl.units > 0) DNLP_LAUNCH_CHECK();
   }
   // Small systems: one workgroup walks all levels (one launch).  Large ones (>= 8192 pivot

@@ -232,7 +232,8 @@ struct Model {
     }
   }
 
-  // row-class segments (op_is_row): M rows of K entries each.  OP_PROD: sweep_prod_segment below.  OP_LOG_SUM_EXP, here:
+  // row-class segments (op_is_row): M rows of K entries each.  OP_PROD: sweep_prod_segment below, OP_QUAD_OVER_LIN_ROWS:
+  // sweep_qol_rows_segment.  OP_LOG_SUM_EXP, here:
   // log_sum_exp over M rows of K entries (lowering.py _lower_log_sum_exp; the reference's
   // log_sum_exp.py tags the atom smooth and has no _jacobian / _hess_vec to follow).  Per row, with mx = max_l u_l and
   // e_l = exp(u_l - mx):
@@ -240,18 +241,20 @@ struct Model {
   // K = 1 gives r = u, p = 1, h = 0 exactly; a row with +inf or NaN gives NaN (inf - inf).  Three maps -- rows, entries,
   // Hessian entries -- so that the in-kernel space runs every stage with all its lanes; (mx, S) of a row wait in tmpN
   // between the first two (rows of K >= 2 distinct entries: 2 M <= N, refused otherwise by Tape::load_rows).  The host-driven device space has kernels of
-  // its own (exec_hip.h sweep_rows_* and sweep_prod_*: one set of row tables per opcode).
+  // its own (exec_hip.h sweep_rows_*, sweep_prod_* and sweep_qol_*: one set of row tables per opcode).
   DNLP_HD void sweep_rows(const double* x, bool with_h) {
     DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
     if (t.nrow == 0) return;
     if constexpr (E::is_device && E::has_host_control) {
       ex->sweep_rows(t.row_short, t.row_long, t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
       ex->sweep_prod(t.row_prod[0], t.row_prod[1], t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
+      ex->sweep_qol(t.row_qol[0], t.row_qol[1], t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
       return;
     }
     for (i64 rk = 0; rk < t.nrow; ++rk) {
       const SegHost& g = t.segs[t.row_segs[rk]];
       if (g.op == OP_PROD) { sweep_prod_segment(g, x, with_h); continue; }
+      if (g.op == OP_QUAD_OVER_LIN_ROWS) { sweep_qol_rows_segment(g, x, with_h); continue; }
       if (g.op != OP_LOG_SUM_EXP) DNLP_FAIL("row-class segment with an unknown opcode");
       const i32* gidx = t.gidx;
       const i64 M = g.d0, K = g.d1, T = K * (K + 1) / 2, a0b = g.a0_base, a0o = g.a0_off;
@@ -365,6 +368,44 @@ struct Model {
       else if (ui != 0.0) h = dv[b + j] / ui;
       else h = pk[2 * r + 1] == 2.0 ? P0 : (P0 != P0 ? P0 : 0.0);
       hv[e] = ww[r] * h;
+    });
+  }
+
+  // OP_QUAD_OVER_LIN_ROWS (lowering.py _lower_QuadOverLinRows): the rule of OP_QUAD_OVER_LIN above, per row.  With
+  // y = x[a1[r]], ss = sum_l u_l^2 (here: left to right) and w = w_r:
+  //   z = ss / y          g_l = 2 u_l / y          g_y = -ss / (y y)
+  //   h_ll = 2 w / y      h_ly = -2 w u_l / (y y)  h_yy = 2 w ss / (y y y)
+  // d: g_l at r K + l, g_y at M K + r.  h: h_ll at r K + l, h_yy at M K + r, h_ly at M K + M + r K + l.  No branch on the
+  // data: a NaN entry poisons z, g_y, h_yy of its row and its own g_l, h_ly; y = 0 gives inf, or NaN where ss = 0.  Two
+  // maps -- rows, entries; the second needs only u, y and w, so nothing of a row is parked between them (and
+  // Tape::load_rows sets no limit on M against N, as it must for the other two members).
+  DNLP_HD void sweep_qol_rows_segment(const SegHost& g, const double* x, bool with_h) {
+    DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
+    const i32* gidx = t.gidx;
+    const i64 M = g.d0, K = g.d1, a0b = g.a0_base, a0o = g.a0_off, a1b = g.a1_base, a1o = g.a1_off;
+    double* z = xz + t.N + g.zoff;
+    double* dv = dvals + g.doff;
+    double* hv = hvals + g.hoff;
+    const double* ww = w + g.zoff;
+    ex->map(M, [=] DNLP_HD(i64 r) {
+      const i64 b = r * K;
+      double ss = 0.0;
+      for (i64 l = 0; l < K; ++l) { const double u = x[a0b >= 0 ? a0b + b + l : gidx[a0o + b + l]]; ss += u * u; }
+      const double y = x[a1b >= 0 ? a1b + r : gidx[a1o + r]];
+      z[r] = ss / y;
+      dv[M * K + r] = -ss / (y * y);
+      if (with_h) hv[M * K + r] = 2.0 * ww[r] * ss / (y * y * y);
+    });
+    ex->map(M * K, [=] DNLP_HD(i64 e) {
+      const i64 r = e / K;
+      const double y = x[a1b >= 0 ? a1b + r : gidx[a1o + r]];
+      const double u = x[a0b >= 0 ? a0b + e : gidx[a0o + e]];
+      dv[e] = 2.0 * u / y;
+      if (with_h) {
+        const double wz = ww[r];
+        hv[e] = 2.0 * wz / y;
+        hv[M * K + M + e] = -2.0 * wz * u / (y * y);
+      }
     });
   }
 

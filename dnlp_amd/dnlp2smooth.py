@@ -160,6 +160,16 @@ def _quad_over_lin(atom, args):
     return _alias_arguments(atom, args, (PLAIN, Aux(nonneg=True, init=init_if_safely_positive)))
 
 
+def _quad_over_lin_rows(atom, args):
+    """The row-wise twin of _quad_over_lin (no reference rule: quad_over_lin.py has no axis)."""
+    num, den = args
+    if den.is_constant():                      # sums of squares along the axis over numbers
+        squares, rows = _canon(at.power(num, 2))
+        scale = 1 / np.asarray(den.value, dtype=float)
+        return at.multiply(Constant(scale), at.Sum(squares, atom.axis, atom.keepdims)), rows
+    return _alias_arguments(atom, args, (PLAIN, Aux(nonneg=True, init=init_if_safely_positive)))
+
+
 def _rel_entr(atom, args):
     """rel_entr_canon.py:29-61: x log(x / y)."""
     x, y = args
@@ -259,11 +269,15 @@ def _sum_largest(atom, args):                   # sum_largest_canon.py:21-32
 
 
 def _pnorm(atom, args):
-    """pnorm_canon.py:22-34 (p = 2 only): t >= 0 with x'x / t <= t."""
+    """pnorm_canon.py:22-34 (p = 2 only): t >= 0 with x'x / t <= t.  A norm along an axis (not scalar: the reference's
+    rule hands the vector t to the scalar-only quad_over_lin and raises) is the same statement per row."""
     if atom.p != 2:
         raise ValueError("Only p=2 is supported as Pnorm.")
     t = Variable(atom.shape, nonneg=True)
-    ratio, rows = _canon(at.quad_over_lin(args[0], t))
+    if not atom.is_scalar():
+        ratio, rows = _canon(at.QuadOverLinRows(args[0], t, atom.axis, atom.keepdims))
+    else:
+        ratio, rows = _canon(at.quad_over_lin(args[0], t))
     return t, rows + [ratio <= t]
 
 
@@ -282,6 +296,7 @@ RULES.update({
     at.multiply: _bilinear,
     at.MulExpression: _bilinear,
     at.quad_over_lin: _quad_over_lin,
+    at.QuadOverLinRows: _quad_over_lin_rows,
     at.rel_entr: _rel_entr,
     # rewrites
     at.kl_div: _kl_div,

@@ -47,6 +47,7 @@ OP_MUL, OP_REL_ENTR = 20, 21
 OP_QUAD_FORM_DENSE, OP_QUAD_FORM_SPARSE, OP_QUAD_OVER_LIN, OP_MATMUL = 30, 31, 32, 33
 OP_LOG_SUM_EXP = 34          # row class: many short (or few long) reductions, one dense Hessian block per row
 OP_PROD = 35                 # row class: the same rows with the STRICT lower triangle (a product's Hessian diagonal is zero)
+OP_QUAD_OVER_LIN_ROWS = 36   # row class with a second argument (one denominator per row); an arrow of 2K + 1 Hessian entries per row
 
 UNARY_OPS = {
     at.exp: OP_EXP, at.log: OP_LOG, at.entr: OP_ENTR, at.logistic: OP_LOGISTIC,
@@ -299,7 +300,7 @@ class Segment:
     hoff: int = 0
     hcount: int = 0
     aux: int = -1               # constant-matrix id (quad_form) / inner dimension (matmul)
-    dims: tuple = (0, 0, 0)     # matmul (m, k, p); log_sum_exp / prod (rows M, row length K, 0)
+    dims: tuple = (0, 0, 0)     # matmul (m, k, p); row class (rows M, row length K, 0)
 
 
 @dataclass
@@ -743,10 +744,9 @@ class Lowerer:
                           np.repeat(z, 2 * n + 1))
         return self._z_form(seg.zoff, 1)
 
-    def _row_class(self, e, name, op, diag):
-        """Row class (csrc/model.h sweep_rows): M rows of K entries, a0[r*K + l] = x index of entry l of row r, one z per
-        row, d[r*K + l] = the row's derivative by entry l, h = the row's lower triangle in tril_indices order, with the
-        diagonal (`diag` = 0) or without it (`diag` = -1)."""
+    def _row_geometry(self, e, name):
+        """(M, K, a0) of an axis atom's first argument: M rows of K entries, a0[r*K + l] = x index of entry l of row r
+        (axis None: one row of everything; 0: one row per column of the F-ordered argument; 1: one per matrix row)."""
         a = e.args[0]
         g = self._gather(a)
         if e.axis is None or a.ndim <= 1:
@@ -759,6 +759,13 @@ class Lowerer:
                 M, K, a0 = a.shape[0], a.shape[1], g.reshape(a.shape, order="F").reshape(-1, order="C")
         if M * K == 0:
             raise ValueError("%s of an empty argument." % name)
+        return M, K, a0
+
+    def _row_class(self, e, name, op, diag):
+        """Row class (csrc/model.h sweep_rows): M rows of K entries (_row_geometry), one z per
+        row, d[r*K + l] = the row's derivative by entry l, h = the row's lower triangle in tril_indices order, with the
+        diagonal (`diag` = 0) or without it (`diag` = -1)."""
+        M, K, a0 = self._row_geometry(e, name)
         T = K * (K + 1) // 2 if diag == 0 else K * (K - 1) // 2
         if self.nh + M * T > 2 ** 31 - 1 or self.nd + M * K > 2 ** 31 - 1:
             raise ValueError("%s: %d row(s) of length %d need %d Hessian entries; the tape's 32-bit index "
@@ -783,6 +790,38 @@ class Lowerer:
         """d[r*K + l] = prod_{k != l} u_k; h: the STRICT lower triangle, (i, j) -> w_r prod_{k != i, j} u_k.  K = 1: no
         Hessian entry, d = 1, z = u."""
         return self._row_class(e, "prod", OP_PROD, -1)
+
+    def _lower_QuadOverLinRows(self, e):
+        """Row class with two arguments: a0 as above, a1[r] = x index of row r's denominator.  d: M K entries dz_r/du_l at
+        r*K + l, then M entries dz_r/dy_r.  h, an arrow per row (2K + 1 entries, not a triangle): M K entries (u_l, u_l)
+        at r*K + l, M entries (y_r, y_r) at M*K + r, M K entries (u_l, y_r) at M*K + M + r*K + l -- the three blocks of
+        _lower_quad_over_lin, each over all rows."""
+        name = "quad_over_lin_rows"
+        M, K, a0 = self._row_geometry(e, name)
+        a1 = self._gather(e.args[1])
+        if a1.size != M:
+            raise ValueError("%s: %d denominator(s) for %d row(s)." % (name, a1.size, M))
+        H = 2 * K + 1
+        if self.nh + M * H > 2 ** 31 - 1 or self.nd + M * (K + 1) > 2 ** 31 - 1:
+            raise ValueError("%s: %d row(s) of length %d need %d Hessian entries; the tape's 32-bit index "
+                             "range ends at %d." % (name, M, K, M * H, 2 ** 31 - 1))
+        rows = a0.reshape(M, K)
+        srt = np.sort(rows, axis=1)
+        if K > 1 and bool(np.any(srt[:, 1:] == srt[:, :-1])):
+            # the diagonal entry would lose the cross term of a repeated index
+            raise ValueError("%s: a row reads the same variable entry twice; its argument must have "
+                             "distinct entries (run dnlp2smooth first)." % name)
+        if bool(np.any(rows == a1[:, None])):
+            # the lower-oriented (u_l, y_r) entry would land on the diagonal and lose its factor 2
+            raise ValueError("%s: a row's denominator is one of its own numerator entries; the two arguments must "
+                             "be distinct variables (run dnlp2smooth first)." % name)
+        seg = Segment(op=OP_QUAD_OVER_LIN_ROWS, n=M, a0=a0, a1=a1, zcount=M, dims=(M, K, 0))
+        z = self.Z + np.arange(M, dtype=np.int64)
+        zk = np.repeat(z, K)
+        a1k = np.repeat(a1, K)
+        self._new_segment(seg, np.concatenate([zk, z]), np.concatenate([a0, a1]),
+                          np.concatenate([a0, a1, a0]), np.concatenate([a0, a1, a1k]), np.concatenate([zk, z, zk]))
+        return self._z_form(seg.zoff, M)
 
 
 def _is_symmetric(P: np.ndarray) -> bool:
