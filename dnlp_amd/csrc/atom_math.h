@@ -18,7 +18,8 @@ enum Op : int {
 };
 
 DNLP_HD inline bool op_is_flat(int op) { return op < OP_QUAD_FORM_DENSE; }
-DNLP_HD inline bool op_is_row(int op) { return op == OP_LOG_SUM_EXP || op == OP_PROD || op == OP_QUAD_OVER_LIN_ROWS; }
+// (constexpr: row_class.h checks its table of members against this at compile time)
+DNLP_HD constexpr inline bool op_is_row(int op) { return op == OP_LOG_SUM_EXP || op == OP_PROD || op == OP_QUAD_OVER_LIN_ROWS; }
 
 // integer-exponent fast paths keep x^2 etc. exact and cheap (pow() is ~50 instructions)
 DNLP_HD inline double pow_fast(double u, double p) {

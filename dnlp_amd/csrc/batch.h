@@ -797,6 +797,7 @@ struct BatchRunner {
     a.base = t;           // slice: the view with the shared exec-space index arrays
     a.base.segs = d_segs; a.base.red_segs = d_red; a.base.row_segs = d_rowsegs; a.base.sparse = d_sparse;
     a.base.dense_ptr = nullptr; a.base.dense_ld = nullptr; a.base.blocks = nullptr;
+    a.base.row_tab = nullptr;        // (host memory, read by the host-driven sweep only)
     a.lay = lay;
     a.batch = batch;
     a.opt = opt;

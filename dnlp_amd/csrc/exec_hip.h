@@ -21,6 +21,7 @@
 
 #include "atom_math.h"
 #include "exec.h"
+#include "row_class.h"
 #include "wave_ops.h"
 #include "bk_panel.h"
 #include <chrono>
@@ -843,459 +844,7 @@ __global__ void __launch_bounds__(kBlock) sweep_flat_kernel(FlatTable t, const d
   }
 }
 
-// ---- tape sweep over the row-class segments (log_sum_exp: hand-written forms of Model::sweep_rows) ----
-// At most three launches per sweep whatever the number of segments and rows: every launch walks a RowTable (tape.h)
-// by its prefix of work.  The order of every sum depends on (K, form) alone: a sweep repeats bit for bit.
-//
-// Short rows (K <= 64): a row is a group of G = next_pow2(K) lanes, 64 / G consecutive rows per wavefront.  max and sum
-// go through an xor butterfly inside the group (every lane ends with the same bits: a + b == b + a), every lane keeps
-// its own p, and the wavefront writes the packed triangles of its rows -- one contiguous run of the Hessian array --
-// with its lanes running linearly over that run (p_i and p_j fetched from the owning lanes).
-__device__ inline void tri_decode(int q, int& i, int& j) {       // q -> (i, j), i >= j, row-major lower triangle; q < 2^23
-  i = static_cast<int>((sqrtf(8.0f * static_cast<float>(q) + 1.0f) - 1.0f) * 0.5f);
-  while (i * (i + 1) / 2 > q) --i;
-  while ((i + 1) * (i + 2) / 2 <= q) ++i;
-  j = q - i * (i + 1) / 2;
-}
-
-__global__ void __launch_bounds__(kBlock) sweep_rows_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
-                                                            double* __restrict__ z, double* __restrict__ dv,
-                                                            double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
-  const int lane = threadIdx.x & 63;
-  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
-  if (wv >= t.units) return;                         // (a whole wavefront leaves: the shuffles below see 64 lanes)
-  i64 lo = 0, hi = t.n;
-  while (hi - lo > 1) {
-    const i64 mid = (lo + hi) >> 1;
-    if (t.start[mid] <= wv) lo = mid; else hi = mid;
-  }
-  const i64 s = lo;
-  const int K = static_cast<int>(t.K[s]);
-  const i64 M = t.M[s];
-  int G = 1, lg = 0;
-  while (G < K) { G <<= 1; ++lg; }
-  const int per = 64 >> lg;
-  const i64 r0 = (wv - t.start[s]) * per;
-  const int l = lane & (G - 1);
-  const i64 r = r0 + (lane >> lg);
-  const bool valid = r < M && l < K;
-  const i64 e = r * K + l;
-  const i64 a0b = t.a0b[s];
-  double u = -kInf;                                  // padding lanes: exp(-inf - mx) = 0
-  if (valid) u = x[a0b >= 0 ? a0b + e : gidx[t.a0o[s] + e]];
-  double mx = u;
-  for (int d = 1; d < G; d <<= 1) mx = fmax(mx, __shfl_xor(mx, d));
-  const double ev = exp(u - mx);
-  double S = ev;
-  for (int d = 1; d < G; d <<= 1) S += __shfl_xor(S, d);
-  const double p = ev / S;
-  if (valid) {
-    dv[t.doff[s] + e] = p;
-    if (l == 0) z[t.zoff[s] + r] = mx + log(S);
-  }
-  if (!with_h) return;
-  const int T = K * (K + 1) / 2;
-  const i64 left = M - r0;
-  const int tot = static_cast<int>(left < per ? left : per) * T;
-  double* __restrict__ hrun = hv + t.hoff[s] + r0 * T;
-  const double* __restrict__ wrow = ww + t.zoff[s] + r0;
-  for (int q0 = 0; q0 < tot; q0 += 64) {             // (uniform trip count: every lane serves the fetches)
-    const int q = q0 + lane;
-    const bool on = q < tot;
-    const int qq = on ? q : 0;
-    const int row = qq / T;
-    int i, j;
-    tri_decode(qq - row * T, i, j);
-    const double pi = __shfl(p, (row << lg) + i), pj = __shfl(p, (row << lg) + j);
-    if (on) hrun[q] = wrow[row] * (i == j ? pi - pi * pj : -(pi * pj));
-  }
-}
-
-// Long rows (K > 64): one wavefront per row (four rows per workgroup) up to kRowWaveMax entries, one 256-lane workgroup
-// per row beyond.  Lane-strided partial max and sum, the wavefront's fixed DPP tree (wave_ops.h), and for the workgroup
-// form its four wavefront totals combined in one fixed order through LDS.  e_l = exp(u_l - mx) is parked in the row's
-// d slots by the lane that later scales it to p_l.  The Hessian entries are not written here (sweep_rows_hess_kernel).
-__global__ void __launch_bounds__(kBlock) sweep_rows_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
-                                                                 double* __restrict__ z, double* __restrict__ dv) {
-  static_assert(kBlock == 256, "four wavefronts per workgroup: Tape::load_rows counts four rows per workgroup, and the combines below read sm[0..3]");
-  __shared__ double sm[kBlock / 64];
-  const i64 b = blockIdx.x;
-  i64 lo = 0, hi = t.n;
-  while (hi - lo > 1) {
-    const i64 mid = (lo + hi) >> 1;
-    if (t.start[mid] <= b) lo = mid; else hi = mid;
-  }
-  const i64 s = lo;
-  const i64 K = t.K[s], M = t.M[s];
-  const bool wg = K > kRowWaveMax;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const i64 row = wg ? b - t.start[s] : (b - t.start[s]) * (kBlock / 64) + wid;
-  const bool rowon = row < M;                        // (wavefront-uniform; the reductions below need all 64 lanes)
-  const int W = wg ? kBlock : 64, tid = wg ? static_cast<int>(threadIdx.x) : lane;
-  const i64 a0b = t.a0b[s], base = row * K;
-  const i32* __restrict__ gi = gidx + t.a0o[s] + base;
-  const double* __restrict__ xr = x + (a0b >= 0 ? a0b + base : 0);
-  double* __restrict__ dr = dv + t.doff[s] + base;
-  const i64 Kon = rowon ? K : 0;
-  double mx = -kInf;
-  for (i64 l = tid; l < Kon; l += W) mx = fmax(mx, a0b >= 0 ? xr[l] : x[gi[l]]);
-  mx = wave_all_max(mx);
-  if (wg) {
-    if (lane == 0) sm[wid] = mx;
-    __syncthreads();
-    mx = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
-    __syncthreads();
-  }
-  double S = 0.0;
-  for (i64 l = tid; l < Kon; l += W) {
-    const double ev = exp((a0b >= 0 ? xr[l] : x[gi[l]]) - mx);
-    dr[l] = ev;
-    S += ev;
-  }
-  S = wave_all_sum(S);
-  if (wg) {
-    if (lane == 0) sm[wid] = S;
-    __syncthreads();
-    S = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
-  for (i64 l = tid; l < Kon; l += W) dr[l] = dr[l] / S;
-  if (rowon && tid == 0) z[t.zoff[s] + row] = mx + log(S);
-}
-
-// The Hessian entries of all long rows spread over the grid: one entry per lane, consecutive addresses per wavefront,
-// each reading p_i (nearly uniform across a wavefront) and p_j (consecutive) from the d slots the launch before filled.
-__global__ void __launch_bounds__(kBlock) sweep_rows_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
-                                                                 const double* __restrict__ ww) {
-  __shared__ i64 s_first;
-  const i64 e_blk = static_cast<i64>(blockIdx.x) * kBlock;
-  if (threadIdx.x == 0) {
-    i64 lo = 0, hi = t.n;
-    while (hi - lo > 1) {
-      const i64 mid = (lo + hi) >> 1;
-      if (t.hstart[mid] <= e_blk) lo = mid; else hi = mid;
-    }
-    s_first = lo;
-  }
-  __syncthreads();
-  const i64 e = e_blk + threadIdx.x;
-  if (e >= t.hunits) return;
-  i64 s = s_first;
-  while (t.hstart[s + 1] <= e) ++s;
-  const unsigned qa = static_cast<unsigned>(e - t.hstart[s]);       // (a segment's entries fit 31 bits: the lowering's limit)
-  const unsigned K = static_cast<unsigned>(t.K[s]), T = K * (K + 1) / 2;
-  const unsigned row = qa / T, q = qa - row * T;
-  unsigned i = static_cast<unsigned>((sqrt(8.0 * static_cast<double>(q) + 1.0) - 1.0) * 0.5);
-  while (i * (i + 1) / 2 > q) --i;
-  while ((i + 1) * (i + 2) / 2 <= q) ++i;
-  const unsigned j = q - i * (i + 1) / 2;
-  const double* __restrict__ pr = dv + t.doff[s] + static_cast<i64>(row) * K;
-  const double pi = pr[i], pj = pr[j];
-  hv[t.hoff[s] + qa] = ww[t.zoff[s] + row] * (i == j ? pi - pi * pj : -(pi * pj));
-}
-
-// ---- the row class, OP_PROD (hand-written forms of Model::sweep_prod_segment; the rule is stated there) ----
-// The same three launches over row tables of their own (tape.h RowTable: one table per opcode and form), so a sweep of a
-// tape that holds log_sum_exp AND prod rows of both lengths is six launches, each over all segments of its kind; a
-// table with an opcode column would make it three, at the price of one kernel text serving both atoms (the registers of
-// the larger, and log_sum_exp's kernels recompiled).  The order of every product depends on (K, form) alone.
-//
-// The product form of the DPP tree of wave_ops.h (not there: that text also travels into the run-time-compiled kernels).
-// Lanes without a source keep the identity, 1.0; lane 63 ends with the wavefront's product, broadcast through an SGPR.
-__device__ inline double wave_all_prod(double v) {
-  v *= dpp_shift_f64<0x111, 0xf>(v, 1.0);
-  v *= dpp_shift_f64<0x112, 0xf>(v, 1.0);
-  v *= dpp_shift_f64<0x114, 0xf>(v, 1.0);
-  v *= dpp_shift_f64<0x118, 0xf>(v, 1.0);
-  v *= dpp_shift_f64<0x142, 0xa>(v, 1.0);
-  v *= dpp_shift_f64<0x143, 0xc>(v, 1.0);
-  return wave_lane63(v);
-}
-__device__ inline int wave_all_sum_i32(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// what the rule writes where it says 0: a NaN product stays NaN
-__device__ inline double prod_zero(double P0) { return P0 != P0 ? P0 : 0.0; }
-
-// Short rows (K <= 64): groups of G = next_pow2(K) lanes as in sweep_rows_kernel; padding lanes and zero entries carry
-// 1.0 into the xor butterfly of the product (a * b == b * a: every lane of a group ends with the same bits), the zeros
-// are counted beside it.  Every lane keeps its g and u; the wavefront writes the STRICT triangles of its rows as one
-// contiguous run, lanes linear over the run.  g_i and u_j come from the owning lanes; the other four values are fetched
-// only by a wavefront that meets u_j == 0 (wavefront-uniform branch: the fetches need all 64 lanes).
-__global__ void __launch_bounds__(kBlock) sweep_prod_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
-                                                            double* __restrict__ z, double* __restrict__ dv,
-                                                            double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
-  const int lane = threadIdx.x & 63;
-  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
-  if (wv >= t.units) return;                         // (a whole wavefront leaves: the shuffles below see 64 lanes)
-  i64 lo = 0, hi = t.n;
-  while (hi - lo > 1) {
-    const i64 mid = (lo + hi) >> 1;
-    if (t.start[mid] <= wv) lo = mid; else hi = mid;
-  }
-  const i64 s = lo;
-  const int K = static_cast<int>(t.K[s]);
-  const i64 M = t.M[s];
-  int G = 1, lg = 0;
-  while (G < K) { G <<= 1; ++lg; }
-  const int per = 64 >> lg;
-  const i64 r0 = (wv - t.start[s]) * per;
-  const int l = lane & (G - 1);
-  const i64 r = r0 + (lane >> lg);
-  const bool valid = r < M && l < K;
-  const i64 e = r * K + l;
-  const i64 a0b = t.a0b[s];
-  double u = 1.0;
-  if (valid) u = x[a0b >= 0 ? a0b + e : gidx[t.a0o[s] + e]];
-  const bool zero = u == 0.0;
-  double P0 = zero ? 1.0 : u;
-  int nz = zero ? 1 : 0;
-  for (int d = 1; d < G; d <<= 1) { P0 *= __shfl_xor(P0, d); nz += __shfl_xor(nz, d); }
-  const double g = nz == 0 ? P0 / u : ((nz == 1 && zero) ? P0 : prod_zero(P0));
-  if (valid) {
-    dv[t.doff[s] + e] = g;
-    if (l == 0) z[t.zoff[s] + r] = nz == 0 ? P0 : prod_zero(P0);
-  }
-  if (!with_h || K < 2) return;
-  const int T = K * (K - 1) / 2;
-  const i64 left = M - r0;
-  const int tot = static_cast<int>(left < per ? left : per) * T;
-  double* __restrict__ hrun = hv + t.hoff[s] + r0 * T;
-  const double* __restrict__ wrow = ww + t.zoff[s] + r0;
-  for (int q0 = 0; q0 < tot; q0 += 64) {             // (uniform trip count: every lane serves the fetches)
-    const int q = q0 + lane;
-    const bool on = q < tot;
-    const int qq = on ? q : 0;
-    const int row = qq / T;
-    int i, j;
-    tri_decode(qq - row * T, i, j);                  // (entry q of the strict triangle = entry q of the full one, a row down)
-    ++i;
-    const int li = (row << lg) + i, lj = (row << lg) + j;
-    const double gi = __shfl(g, li), uj = __shfl(u, lj);
-    double h = gi / (uj == 0.0 ? 1.0 : uj);          // (no division by zero, not even in a value that is replaced below)
-    if (__any(on && uj == 0.0)) {
-      const double gj = __shfl(g, lj), ui = __shfl(u, li), Pr = __shfl(P0, li);
-      const int nr = __shfl(nz, li);
-      if (uj == 0.0) h = ui != 0.0 ? gj / ui : (nr == 2 ? Pr : prod_zero(Pr));
-    }
-    if (on) hrun[q] = wrow[row] * h;
-  }
-}
-
-// Long rows (K > 64): one wavefront per row (four rows per workgroup) up to kRowWaveMax entries, one 256-lane workgroup
-// per row beyond, as sweep_rows_long_kernel.  Lane-strided partial products and zero counts, the DPP tree above, and for
-// the workgroup form the four wavefront totals combined in one fixed order through LDS.  g needs u once more (re-read:
-// nothing is parked in the d slots).  With the Hessian on, two things wait in the table's park array for the next launch:
-// what it cannot rebuild from g and u -- the entry of two zero positions, nz == 2 ? P0 : Z0, one double per row -- and a
-// contiguous copy of the row (an axis-1 row of an F-ordered argument lies strided in x, and the Hessian launch reads u_j
-// with consecutive j in consecutive lanes).
-__global__ void __launch_bounds__(kBlock) sweep_prod_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
-                                                                 double* __restrict__ z, double* __restrict__ dv, int with_h) {
-  static_assert(kBlock == 256, "four wavefronts per workgroup: Tape::load_rows counts four rows per workgroup, and the combines below read sm[0..3]");
-  __shared__ double sm[kBlock / 64];
-  __shared__ int sn[kBlock / 64];
-  const i64 b = blockIdx.x;
-  i64 lo = 0, hi = t.n;
-  while (hi - lo > 1) {
-    const i64 mid = (lo + hi) >> 1;
-    if (t.start[mid] <= b) lo = mid; else hi = mid;
-  }
-  const i64 s = lo;
-  const i64 K = t.K[s], M = t.M[s];
-  const bool wg = K > kRowWaveMax;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const i64 row = wg ? b - t.start[s] : (b - t.start[s]) * (kBlock / 64) + wid;
-  const bool rowon = row < M;                        // (wavefront-uniform; the reductions below need all 64 lanes)
-  const int W = wg ? kBlock : 64, tid = wg ? static_cast<int>(threadIdx.x) : lane;
-  const i64 a0b = t.a0b[s], base = row * K;
-  const i32* __restrict__ gi = gidx + t.a0o[s] + base;
-  const double* __restrict__ xr = x + (a0b >= 0 ? a0b + base : 0);
-  double* __restrict__ dr = dv + t.doff[s] + base;
-  const i64 Kon = rowon ? K : 0;
-  double P0 = 1.0;
-  int nz = 0;
-  for (i64 l = tid; l < Kon; l += W) {
-    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
-    if (u == 0.0) ++nz; else P0 *= u;
-  }
-  P0 = wave_all_prod(P0);
-  nz = wave_all_sum_i32(nz);
-  if (wg) {
-    if (lane == 0) { sm[wid] = P0; sn[wid] = nz; }
-    __syncthreads();
-    P0 = (sm[0] * sm[1]) * (sm[2] * sm[3]);
-    nz = (sn[0] + sn[1]) + (sn[2] + sn[3]);
-  }
-  const double Z0 = prod_zero(P0);
-  double* __restrict__ ur = t.park + 4 * t.units + t.ustart[s] + base;
-  for (i64 l = tid; l < Kon; l += W) {
-    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
-    dr[l] = nz == 0 ? P0 / u : ((nz == 1 && u == 0.0) ? P0 : Z0);
-    if (with_h) ur[l] = u;
-  }
-  if (rowon && tid == 0) {
-    z[t.zoff[s] + row] = nz == 0 ? P0 : Z0;
-    if (with_h) t.park[4 * t.start[s] + row] = nz == 2 ? P0 : Z0;
-  }
-}
-
-// The strict-triangle entries of all long rows spread over the grid as in sweep_rows_hess_kernel: one entry per lane,
-// g from the d slots and u from the copy the launch before filled.
-__global__ void __launch_bounds__(kBlock) sweep_prod_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
-                                                                 const double* __restrict__ ww) {
-  __shared__ i64 s_first;
-  const i64 e_blk = static_cast<i64>(blockIdx.x) * kBlock;
-  if (threadIdx.x == 0) {
-    i64 lo = 0, hi = t.n;
-    while (hi - lo > 1) {
-      const i64 mid = (lo + hi) >> 1;
-      if (t.hstart[mid] <= e_blk) lo = mid; else hi = mid;
-    }
-    s_first = lo;
-  }
-  __syncthreads();
-  const i64 e = e_blk + threadIdx.x;
-  if (e >= t.hunits) return;
-  i64 s = s_first;
-  while (t.hstart[s + 1] <= e) ++s;
-  const unsigned qa = static_cast<unsigned>(e - t.hstart[s]);       // (a segment's entries fit 31 bits: the lowering's limit)
-  const unsigned K = static_cast<unsigned>(t.K[s]), T = K * (K - 1) / 2;
-  const unsigned row = qa / T, q = qa - row * T;
-  unsigned i = static_cast<unsigned>((sqrt(8.0 * static_cast<double>(q) + 1.0) - 1.0) * 0.5);
-  while (i * (i + 1) / 2 > q) --i;
-  while ((i + 1) * (i + 2) / 2 <= q) ++i;
-  const unsigned j = q - i * (i + 1) / 2;
-  ++i;
-  const i64 base = static_cast<i64>(row) * K;
-  const double* __restrict__ gr = dv + t.doff[s] + base;
-  const double* __restrict__ ur = t.park + 4 * t.units + t.ustart[s] + base;
-  const double uj = ur[j];
-  double h;
-  if (uj != 0.0) h = gr[i] / uj;
-  else {
-    const double ui = ur[i];
-    h = ui != 0.0 ? gr[j] / ui : t.park[4 * t.start[s] + row];
-  }
-  hv[t.hoff[s] + qa] = ww[t.zoff[s] + row] * h;
-}
-
-// ---- the row class, OP_QUAD_OVER_LIN_ROWS (hand-written forms of Model::sweep_qol_rows_segment; the rule is stated there) ----
-// Two tables of their own (tape.h RowTable, with the a1 columns), two kernels, at most two launches per sweep for all
-// segments of the op: a row's Hessian is an arrow of 2K + 1 entries, written by the lanes that hold u_l, so there is no
-// third launch and no packed-index decode.  No floating-point atomics; the order of ss depends on (K, form) alone.
-//
-// Short rows (K <= 64): groups of G = next_pow2(K) lanes as in sweep_rows_kernel (K = 2, 3: 32 and 16 rows per
-// wavefront).  u^2 goes through the xor butterfly inside the group, padding lanes carry 0 (a + b == b + a: every lane of
-// a group ends with the same bits).  Every lane of a group reads the group's y and w (one address per group: the
-// hardware merges them) and writes its g_l, h_ll, h_ly at r K + l -- across the wavefront consecutive addresses in each
-// of the three blocks; lane 0 of the group writes z, g_y, h_yy.  No LDS.
-__global__ void __launch_bounds__(kBlock) sweep_qol_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
-                                                           double* __restrict__ z, double* __restrict__ dv,
-                                                           double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
-  const int lane = threadIdx.x & 63;
-  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
-  if (wv >= t.units) return;                         // (a whole wavefront leaves: the shuffles below see 64 lanes)
-  i64 lo = 0, hi = t.n;
-  while (hi - lo > 1) {
-    const i64 mid = (lo + hi) >> 1;
-    if (t.start[mid] <= wv) lo = mid; else hi = mid;
-  }
-  const i64 s = lo;
-  const int K = static_cast<int>(t.K[s]);
-  const i64 M = t.M[s];
-  int G = 1, lg = 0;
-  while (G < K) { G <<= 1; ++lg; }
-  const int per = 64 >> lg;
-  const i64 r0 = (wv - t.start[s]) * per;
-  const int l = lane & (G - 1);
-  const i64 r = r0 + (lane >> lg);
-  const bool valid = r < M && l < K;
-  const i64 e = r * K + l;
-  const i64 a0b = t.a0b[s];
-  double u = 0.0;
-  if (valid) u = x[a0b >= 0 ? a0b + e : gidx[t.a0o[s] + e]];
-  double ss = u * u;
-  for (int d = 1; d < G; d <<= 1) ss += __shfl_xor(ss, d);
-  if (!valid) return;                                // (no exchange between lanes from here on)
-  const i64 a1b = t.a1b[s], MK = M * K;
-  const double y = x[a1b >= 0 ? a1b + r : gidx[t.a1o[s] + r]];
-  double* __restrict__ ds = dv + t.doff[s];
-  ds[e] = 2.0 * u / y;
-  if (l == 0) {
-    z[t.zoff[s] + r] = ss / y;
-    ds[MK + r] = -ss / (y * y);
-  }
-  if (!with_h) return;
-  const double w = ww[t.zoff[s] + r];
-  double* __restrict__ hs = hv + t.hoff[s];
-  hs[e] = 2.0 * w / y;
-  hs[MK + M + e] = -2.0 * w * u / (y * y);
-  if (l == 0) hs[MK + r] = 2.0 * w * ss / (y * y * y);
-}
-
-// Long rows (K > 64): one wavefront per row (four rows per workgroup) up to kRowWaveMax entries, one 256-lane workgroup
-// per row beyond, as sweep_rows_long_kernel.  Lane-strided partial sums of u^2, the fixed DPP tree (wave_ops.h), and for
-// the workgroup form the four wavefront totals combined in one order through LDS; then a second lane-strided pass over
-// the row (u re-read: a row of 8 K bytes that the first pass has just brought in) writes g and both Hessian blocks.
-__global__ void __launch_bounds__(kBlock) sweep_qol_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
-                                                                double* __restrict__ z, double* __restrict__ dv,
-                                                                double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
-  static_assert(kBlock == 256, "four wavefronts per workgroup: Tape::load_rows counts four rows per workgroup, and the combine below reads sm[0..3]");
-  __shared__ double sm[kBlock / 64];
-  const i64 b = blockIdx.x;
-  i64 lo = 0, hi = t.n;
-  while (hi - lo > 1) {
-    const i64 mid = (lo + hi) >> 1;
-    if (t.start[mid] <= b) lo = mid; else hi = mid;
-  }
-  const i64 s = lo;
-  const i64 K = t.K[s], M = t.M[s];
-  const bool wg = K > kRowWaveMax;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const i64 row = wg ? b - t.start[s] : (b - t.start[s]) * (kBlock / 64) + wid;
-  const bool rowon = row < M;                        // (wavefront-uniform; the reduction below needs all 64 lanes)
-  const int W = wg ? kBlock : 64, tid = wg ? static_cast<int>(threadIdx.x) : lane;
-  const i64 a0b = t.a0b[s], base = row * K;
-  const i32* __restrict__ gi = gidx + t.a0o[s] + base;
-  const double* __restrict__ xr = x + (a0b >= 0 ? a0b + base : 0);
-  const i64 Kon = rowon ? K : 0;
-  double ss = 0.0;
-  for (i64 l = tid; l < Kon; l += W) {
-    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
-    ss += u * u;
-  }
-  ss = wave_all_sum(ss);
-  if (wg) {                                          // (uniform over the workgroup: every wavefront meets the barrier)
-    if (lane == 0) sm[wid] = ss;
-    __syncthreads();
-    ss = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
-  if (!rowon) return;
-  const i64 a1b = t.a1b[s], MK = M * K;
-  const double y = x[a1b >= 0 ? a1b + row : gidx[t.a1o[s] + row]];
-  const double w = with_h ? ww[t.zoff[s] + row] : 0.0;
-  double* __restrict__ dr = dv + t.doff[s] + base;
-  double* __restrict__ hd = hv + t.hoff[s] + base;
-  double* __restrict__ hc = hv + t.hoff[s] + MK + M + base;
-  for (i64 l = tid; l < K; l += W) {
-    const double u = a0b >= 0 ? xr[l] : x[gi[l]];
-    dr[l] = 2.0 * u / y;
-    if (with_h) {
-      hd[l] = 2.0 * w / y;
-      hc[l] = -2.0 * w * u / (y * y);
-    }
-  }
-  if (tid == 0) {
-    z[t.zoff[s] + row] = ss / y;
-    dv[t.doff[s] + MK + row] = -ss / (y * y);
-    if (with_h) hv[t.hoff[s] + MK + row] = 2.0 * w * ss / (y * y * y);
-  }
-}
+#include "exec_hip_rows.h"     // the row-class segments: sweep_rows_* / sweep_prod_* / sweep_qol_* kernels
 
 // part[q * 1024 + block] = this block's share of sum_i V[q*N + i] * w[i] for q < k (k <= 32): all k dot products in one
 // sweep of w; vt_dot_finish_kernel adds the blocks' shares in block order (round 4: an atomic add per block landed in
@@ -1816,42 +1365,31 @@ struct HipExec : HostControlled {
                        with_h ? 1 : 0);
     DNLP_LAUNCH_CHECK();
   }
-  void sweep_rows(const RowTable& ts, const RowTable& tl, const i32* gidx, const double* x, double* z, double* dv, double* hv,
-                  const double* w, bool with_h) {
-    if (ts.units > 0)
-      hipLaunchKernelGGL(sweep_rows_kernel, dim3(static_cast<unsigned>((ts.units + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
-                         stream, ts, gidx, x, z, dv, hv, w, with_h ? 1 : 0);
-    if (tl.units > 0) {
-      hipLaunchKernelGGL(sweep_rows_long_kernel, dim3(static_cast<unsigned>(tl.units)), dim3(kBlock), 0, stream, tl, gidx, x, z, dv);
-      if (with_h)
-        hipLaunchKernelGGL(sweep_rows_hess_kernel, dim3(static_cast<unsigned>((tl.hunits + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           tl, dv, hv, w);
-    }
-    DNLP_LAUNCH_CHECK();
-  }
-  void sweep_prod(const RowTable& ts, const RowTable& tl, const i32* gidx, const double* x, double* z, double* dv, double* hv,
-                  const double* w, bool with_h) {
-    if (ts.units > 0)
-      hipLaunchKernelGGL(sweep_prod_kernel, dim3(static_cast<unsigned>((ts.units + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
-                         stream, ts, gidx, x, z, dv, hv, w, with_h ? 1 : 0);
-    if (tl.units > 0) {
-      hipLaunchKernelGGL(sweep_prod_long_kernel, dim3(static_cast<unsigned>(tl.units)), dim3(kBlock), 0, stream, tl, gidx, x, z, dv,
-                         with_h ? 1 : 0);
-      if (with_h)
-        hipLaunchKernelGGL(sweep_prod_hess_kernel, dim3(static_cast<unsigned>((tl.hunits + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           tl, dv, hv, w);
-    }
-    if (ts.units > 0 || tl.units > 0) DNLP_LAUNCH_CHECK();
-  }
-  void sweep_qol(const RowTable& ts, const RowTable& tl, const i32* gidx, const double* x, double* z, double* dv, double* hv,
-                 const double* w, bool with_h) {
-    if (ts.units > 0)
-      hipLaunchKernelGGL(sweep_qol_kernel, dim3(static_cast<unsigned>((ts.units + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
-                         stream, ts, gidx, x, z, dv, hv, w, with_h ? 1 : 0);
-    if (tl.units > 0)
-      hipLaunchKernelGGL(sweep_qol_long_kernel, dim3(static_cast<unsigned>(tl.units)), dim3(kBlock), 0, stream, tl, gidx, x, z, dv, hv, w,
-                         with_h ? 1 : 0);
-    if (ts.units > 0 || tl.units > 0) DNLP_LAUNCH_CHECK();
+  // the row-class segments (exec_hip_rows.h): `tab` is TapeView::row_tab, [member][form]; per member the short form, the
+  // long form and, where the member has one and the Hessian is asked for, the spread Hessian launch
+  void sweep_row_tables(const RowTable* tab, const i32* gidx, const double* x, double* z, double* dv, double* hv, const double* w,
+                        bool with_h) {
+    const int h = with_h ? 1 : 0;
+    int launched = 0;
+    auto go = [&](auto kernel, i64 blocks, auto... args) {
+      if (blocks <= 0) return;
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, args...);
+      ++launched;
+    };
+    auto waves = [](const RowTable& t) { return (t.units + kBlock / 64 - 1) / (kBlock / 64); };
+    auto spread = [&](const RowTable& t) { return with_h && t.units > 0 ? (t.hunits + kBlock - 1) / kBlock : 0; };
+    const RowTable &ls = tab[0], &ll = tab[1], &ps = tab[2], &pl = tab[3], &qs = tab[4], &ql = tab[5];
+    static_assert(kRowMembers == 3 && kRowForms == 2 && row_member(0).op == OP_LOG_SUM_EXP && row_member(1).op == OP_PROD &&
+                  row_member(2).op == OP_QUAD_OVER_LIN_ROWS, "the launches below follow the table of members");
+    go(sweep_rows_kernel, waves(ls), ls, gidx, x, z, dv, hv, w, h);
+    go(sweep_rows_long_kernel, ll.units, ll, gidx, x, z, dv);
+    go(sweep_rows_hess_kernel, spread(ll), ll, static_cast<const double*>(dv), hv, w);
+    go(sweep_prod_kernel, waves(ps), ps, gidx, x, z, dv, hv, w, h);
+    go(sweep_prod_long_kernel, pl.units, pl, gidx, x, z, dv, h);
+    go(sweep_prod_hess_kernel, spread(pl), pl, static_cast<const double*>(dv), hv, w);
+    go(sweep_qol_kernel, waves(qs), qs, gidx, x, z, dv, hv, w, h);
+    go(sweep_qol_long_kernel, ql.units, ql, gidx, x, z, dv, hv, w, h);
+    if (launched) DNLP_LAUNCH_CHECK();
   }
   // Small systems: one workgroup walks all levels (one launch).  Large ones (>= 8192 pivot
   // blocks): one grid-wide kernel per level phase, sized by that level's blocks / rows / triples.

@@ -1,0 +1,407 @@
+// Tape sweep over the row-class segments in the host-driven device space: the hand-written forms of the rules that
+// model.h states (sweep_lse_segment, sweep_prod_segment, sweep_qol_rows_segment).  Included by exec_hip.h.
+//
+// Every launch walks one RowTable (row_class.h: the segments of one member in one kernel form) by its prefix of work, so
+// a sweep is at most eight launches whatever the number of segments and rows, and a kernel serves one member (a table
+// with an opcode column would make it three launches, at the price of one kernel text with the registers of the largest
+// member).  The order of every sum and product depends on (K, form) alone: a sweep repeats bit for bit.  No
+// floating-point atomics.
+//
+//   short form (K <= 64)     a row is a group of G = next_pow2(K) lanes, 64 / G consecutive rows per wavefront.  Reductions
+//                            go through an xor butterfly inside the group (a + b == b + a: every lane of a group ends with
+//                            the same bits), padding lanes carry the operation's identity.  Every lane keeps what it
+//                            computed; a member with a packed triangle has the wavefront write the triangles of its rows
+//                            -- one contiguous run of the Hessian array -- with its lanes linear over that run.
+//   long form (K > 64)       one wavefront per row (four rows per workgroup) up to kRowWaveMax entries, one 256-lane
+//                            workgroup per row beyond.  Lane-strided partial results, the wavefront's fixed DPP tree, and
+//                            for the workgroup form its four wavefront totals combined in one fixed order through LDS.
+//   spread Hessian launch    (members with a packed triangle) the entries of all long rows over the grid: one entry per
+//                            lane, consecutive addresses per wavefront, reading what the launch before left in the d slots
+//                            (and, for prod, in RowTable::park).
+#pragma once
+
+// ---- what the kernels share ----
+// the table row whose prefix interval [start[s], start[s + 1]) holds unit u
+__device__ __forceinline__ i64 row_find(const i64* __restrict__ start, i64 n, i64 u) {
+  i64 lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const i64 mid = (lo + hi) >> 1;
+    if (start[mid] <= u) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// the same for a launch of one unit per lane: lane 0 searches for the workgroup's first unit u_blk and hands the row on
+// through LDS (every lane of the workgroup meets the barrier); a lane then walks on from there to its own unit
+__device__ __forceinline__ i64 row_find_block(const i64* __restrict__ start, i64 n, i64 u_blk) {
+  __shared__ i64 s_first;
+  if (threadIdx.x == 0) s_first = row_find(start, n, u_blk);
+  __syncthreads();
+  return s_first;
+}
+
+// Short form: where this lane stands.  Segment s; its wavefront's first row r0; the lane's row r, its entry l of the row,
+// e = r K + l; u = that entry of the argument, `pad` in the lanes that have none (!valid).  false: the whole wavefront has
+// no work and leaves (the shuffles of the others see 64 lanes).
+struct ShortRow {
+  i64 s, M, r0, r, e;
+  int K, G, lg, per, lane, l;
+  bool valid;
+  double u;
+};
+__device__ __forceinline__ bool short_row(const RowTable& t, const i32* __restrict__ gidx, const double* __restrict__ x, double pad,
+                                          ShortRow& w) {
+  const int lane = threadIdx.x & 63;
+  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  if (wv >= t.units) return false;
+  const i64 s = row_find(t.start, t.n, wv);
+  const int K = static_cast<int>(t.K[s]);
+  const i64 M = t.M[s];
+  int G = 1, lg = 0;
+  while (G < K) { G <<= 1; ++lg; }
+  const int per = 64 >> lg;
+  const i64 r0 = (wv - t.start[s]) * per;
+  const int l = lane & (G - 1);
+  const i64 r = r0 + (lane >> lg);
+  const bool valid = r < M && l < K;
+  const i64 e = r * K + l;
+  const i64 a0b = t.a0b[s];
+  double u = pad;
+  if (valid) u = x[a0b >= 0 ? a0b + e : gidx[t.a0o[s] + e]];
+  w = ShortRow{s, M, r0, r, e, K, G, lg, per, lane, l, valid, u};
+  return true;
+}
+
+// Short form: the wavefront walks the packed triangles (T entries each, `strict`: without the diagonal) of its rows, one
+// contiguous run of the Hessian array.  entry(row, i, j, on) gives h_ij of the wavefront's row `row` before its weight;
+// EVERY lane calls it in every trip (uniform trip count), so it may fetch from the lanes that own i and j.
+template <class F>
+__device__ __forceinline__ void short_row_triangles(const RowTable& t, const ShortRow& w, int T, bool strict, double* __restrict__ hv,
+                                                    const double* __restrict__ ww, F entry) {
+  const i64 left = w.M - w.r0;
+  const int tot = static_cast<int>(left < w.per ? left : w.per) * T;
+  double* __restrict__ hrun = hv + t.hoff[w.s] + w.r0 * T;
+  const double* __restrict__ wrow = ww + t.zoff[w.s] + w.r0;
+  for (int q0 = 0; q0 < tot; q0 += 64) {
+    const int q = q0 + w.lane;
+    const bool on = q < tot;
+    const int qq = on ? q : 0;
+    const int row = qq / T;
+    int i, j;
+    tri_decode(qq - row * T, i, j);
+    if (strict) ++i;
+    const double h = entry(row, i, j, on);
+    if (on) hrun[q] = wrow[row] * h;
+  }
+}
+
+// Long form: where this lane stands.  Segment s; `row` of it (rowon: it exists -- wavefront-uniform, and the reductions
+// need all 64 lanes, so a wavefront without a row walks Kon = 0 entries instead of leaving); the row is walked by W lanes,
+// this one is tid of them: for (l = tid; l < Kon; l += W) ... u(l).  wg: the W = 256 lanes of the workgroup.
+struct LongRow {
+  i64 s, K, M, row, base, Kon, a0b;
+  bool wg, rowon;
+  int lane, wid, W, tid;
+  const i32* __restrict__ gi;
+  const double* __restrict__ xr;
+  const double* __restrict__ x;
+  __device__ __forceinline__ double u(i64 l) const { return a0b >= 0 ? xr[l] : x[gi[l]]; }
+};
+__device__ __forceinline__ LongRow long_row(const RowTable& t, const i32* __restrict__ gidx, const double* __restrict__ x) {
+  static_assert(kBlock == 256, "four wavefronts per workgroup: Tape::load_rows counts four rows per workgroup, and wg_fold reads sm[0..3]");
+  const i64 b = blockIdx.x;
+  const i64 s = row_find(t.start, t.n, b);
+  const i64 K = t.K[s], M = t.M[s];
+  const bool wg = K > kRowWaveMax;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const i64 row = wg ? b - t.start[s] : (b - t.start[s]) * (kBlock / 64) + wid;
+  const bool rowon = row < M;
+  const int W = wg ? kBlock : 64, tid = wg ? static_cast<int>(threadIdx.x) : lane;
+  const i64 a0b = t.a0b[s], base = row * K;
+  const i32* __restrict__ gi = gidx + t.a0o[s] + base;
+  const double* __restrict__ xr = x + (a0b >= 0 ? a0b + base : 0);
+  const i64 Kon = rowon ? K : 0;
+  return LongRow{s, K, M, row, base, Kon, a0b, wg, rowon, lane, wid, W, tid, gi, xr, x};
+}
+
+// Long form, one workgroup per row: the four wavefront totals through sm[0..3], combined as (a0 . a1) . (a2 . a3).
+// (wg_post, a barrier, wg_fold; the condition around them is uniform over the workgroup: every wavefront meets the barrier)
+template <class T>
+__device__ __forceinline__ void wg_post(T* sm, const LongRow& w, T v) { if (w.lane == 0) sm[w.wid] = v; }
+template <class T, class F>
+__device__ __forceinline__ T wg_fold(const T* sm, F op) { return op(op(sm[0], sm[1]), op(sm[2], sm[3])); }
+template <class T, class F>
+__device__ __forceinline__ T wg_combine(T* sm, const LongRow& w, T v, F op) {
+  wg_post(sm, w, v);
+  __syncthreads();
+  return wg_fold(sm, op);
+}
+struct OpAdd { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+struct OpMul { __device__ __forceinline__ double operator()(double a, double b) const { return a * b; } };
+struct OpMax { __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); } };
+
+// Spread Hessian launch: where this lane's entry stands.  Segment s, entry qa of the segment = entry (i, j) of the packed
+// triangle of its row `row`.  false: the lane has no entry.
+struct SpreadEntry {
+  i64 s;
+  unsigned K, row, i, j, qa;
+};
+__device__ __forceinline__ bool spread_entry(const RowTable& t, bool strict, SpreadEntry& en) {
+  const i64 e_blk = static_cast<i64>(blockIdx.x) * kBlock;
+  i64 s = row_find_block(t.hstart, t.n, e_blk);
+  const i64 e = e_blk + threadIdx.x;
+  if (e >= t.hunits) return false;
+  while (t.hstart[s + 1] <= e) ++s;
+  const unsigned qa = static_cast<unsigned>(e - t.hstart[s]);       // (a segment's entries fit 31 bits: the lowering's limit)
+  const unsigned K = static_cast<unsigned>(t.K[s]), T = strict ? K * (K - 1) / 2 : K * (K + 1) / 2;
+  const unsigned row = qa / T;
+  unsigned i, j;
+  tri_decode(qa - row * T, strict, i, j);
+  en = SpreadEntry{s, K, row, i, j, qa};
+  return true;
+}
+
+// The product form of the DPP tree of wave_ops.h (not there: that text also travels into the run-time-compiled kernels).
+// Lanes without a source keep the identity, 1.0; lane 63 ends with the wavefront's product, broadcast through an SGPR.
+__device__ inline double wave_all_prod(double v) {
+  v *= dpp_shift_f64<0x111, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x112, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x114, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x118, 0xf>(v, 1.0);
+  v *= dpp_shift_f64<0x142, 0xa>(v, 1.0);
+  v *= dpp_shift_f64<0x143, 0xc>(v, 1.0);
+  return wave_lane63(v);
+}
+__device__ inline int wave_all_sum_i32(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
+  return __builtin_amdgcn_readlane(v, 63);
+}
+
+// ---- log_sum_exp ----
+// Short rows: max and sum through the butterfly (padding lanes: exp(-inf - mx) = 0), every lane keeps its p; p_i and p_j
+// of a Hessian entry come from the owning lanes.
+__global__ void __launch_bounds__(kBlock) sweep_rows_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                            double* __restrict__ z, double* __restrict__ dv,
+                                                            double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  ShortRow w;
+  if (!short_row(t, gidx, x, -kInf, w)) return;
+  double mx = w.u;
+  for (int d = 1; d < w.G; d <<= 1) mx = fmax(mx, __shfl_xor(mx, d));
+  const double ev = exp(w.u - mx);
+  double S = ev;
+  for (int d = 1; d < w.G; d <<= 1) S += __shfl_xor(S, d);
+  const double p = ev / S;
+  if (w.valid) {
+    dv[t.doff[w.s] + w.e] = p;
+    if (w.l == 0) z[t.zoff[w.s] + w.r] = mx + log(S);
+  }
+  if (!with_h) return;
+  const int lg = w.lg;
+  short_row_triangles(t, w, w.K * (w.K + 1) / 2, false, hv, ww, [=](int row, int i, int j, bool) {
+    const double pi = __shfl(p, (row << lg) + i), pj = __shfl(p, (row << lg) + j);
+    return i == j ? pi - pi * pj : -(pi * pj);
+  });
+}
+
+// Long rows: e_l = exp(u_l - mx) is parked in the row's d slots by the lane that later scales it to p_l.  The Hessian
+// entries are written by sweep_rows_hess_kernel.
+__global__ void __launch_bounds__(kBlock) sweep_rows_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                 double* __restrict__ z, double* __restrict__ dv) {
+  __shared__ double sm[kBlock / 64];
+  const LongRow w = long_row(t, gidx, x);
+  double* __restrict__ dr = dv + t.doff[w.s] + w.base;
+  double mx = -kInf;
+  for (i64 l = w.tid; l < w.Kon; l += w.W) mx = fmax(mx, w.u(l));
+  mx = wave_all_max(mx);
+  if (w.wg) {
+    mx = wg_combine(sm, w, mx, OpMax());
+    __syncthreads();                                 // (sm is posted to once more below)
+  }
+  double S = 0.0;
+  for (i64 l = w.tid; l < w.Kon; l += w.W) {
+    const double ev = exp(w.u(l) - mx);
+    dr[l] = ev;
+    S += ev;
+  }
+  S = wave_all_sum(S);
+  if (w.wg) S = wg_combine(sm, w, S, OpAdd());
+  for (i64 l = w.tid; l < w.Kon; l += w.W) dr[l] = dr[l] / S;
+  if (w.rowon && w.tid == 0) z[t.zoff[w.s] + w.row] = mx + log(S);
+}
+
+// p_i (nearly uniform across a wavefront) and p_j (consecutive) from the d slots the launch before filled
+__global__ void __launch_bounds__(kBlock) sweep_rows_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
+                                                                 const double* __restrict__ ww) {
+  SpreadEntry en;
+  if (!spread_entry(t, false, en)) return;
+  const double* __restrict__ pr = dv + t.doff[en.s] + static_cast<i64>(en.row) * en.K;
+  const double pi = pr[en.i], pj = pr[en.j];
+  hv[t.hoff[en.s] + en.qa] = ww[t.zoff[en.s] + en.row] * (en.i == en.j ? pi - pi * pj : -(pi * pj));
+}
+
+// ---- prod ----
+// what the rule writes where it says 0: a NaN product stays NaN
+__device__ inline double prod_zero(double P0) { return P0 != P0 ? P0 : 0.0; }
+
+// Short rows: padding lanes and zero entries carry 1.0 into the butterfly of the product, the zeros are counted beside
+// it.  Every lane keeps its g and u.  g_i and u_j of a Hessian entry come from the owning lanes; the other four values are
+// fetched only by a wavefront that meets u_j == 0 (wavefront-uniform branch: the fetches need all 64 lanes).
+__global__ void __launch_bounds__(kBlock) sweep_prod_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                            double* __restrict__ z, double* __restrict__ dv,
+                                                            double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  ShortRow w;
+  if (!short_row(t, gidx, x, 1.0, w)) return;
+  const double u = w.u;
+  const bool zero = u == 0.0;
+  double P0 = zero ? 1.0 : u;
+  int nz = zero ? 1 : 0;
+  for (int d = 1; d < w.G; d <<= 1) { P0 *= __shfl_xor(P0, d); nz += __shfl_xor(nz, d); }
+  const double g = nz == 0 ? P0 / u : ((nz == 1 && zero) ? P0 : prod_zero(P0));
+  if (w.valid) {
+    dv[t.doff[w.s] + w.e] = g;
+    if (w.l == 0) z[t.zoff[w.s] + w.r] = nz == 0 ? P0 : prod_zero(P0);
+  }
+  if (!with_h || w.K < 2) return;
+  const int lg = w.lg;
+  short_row_triangles(t, w, w.K * (w.K - 1) / 2, true, hv, ww, [=](int row, int i, int j, bool on) {
+    const int li = (row << lg) + i, lj = (row << lg) + j;
+    const double gi = __shfl(g, li), uj = __shfl(u, lj);
+    double h = gi / (uj == 0.0 ? 1.0 : uj);          // (no division by zero, not even in a value that is replaced below)
+    if (__any(on && uj == 0.0)) {
+      const double gj = __shfl(g, lj), ui = __shfl(u, li), Pr = __shfl(P0, li);
+      const int nr = __shfl(nz, li);
+      if (uj == 0.0) h = ui != 0.0 ? gj / ui : (nr == 2 ? Pr : prod_zero(Pr));
+    }
+    return h;
+  });
+}
+
+// Long rows: g needs u once more (re-read: nothing is parked in the d slots).  With the Hessian on, two things wait in
+// the table's park array for the next launch: what it cannot rebuild from g and u -- the entry of two zero positions,
+// nz == 2 ? P0 : Z0, one double per row -- and a contiguous copy of the row (an axis-1 row of an F-ordered argument lies
+// strided in x, and the Hessian launch reads u_j with consecutive j in consecutive lanes).
+__global__ void __launch_bounds__(kBlock) sweep_prod_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                 double* __restrict__ z, double* __restrict__ dv, int with_h) {
+  __shared__ double sm[kBlock / 64];
+  __shared__ int sn[kBlock / 64];
+  const LongRow w = long_row(t, gidx, x);
+  double* __restrict__ dr = dv + t.doff[w.s] + w.base;
+  double P0 = 1.0;
+  int nz = 0;
+  for (i64 l = w.tid; l < w.Kon; l += w.W) {
+    const double u = w.u(l);
+    if (u == 0.0) ++nz; else P0 *= u;
+  }
+  P0 = wave_all_prod(P0);
+  nz = wave_all_sum_i32(nz);
+  if (w.wg) {
+    wg_post(sm, w, P0);
+    wg_post(sn, w, nz);
+    __syncthreads();
+    P0 = wg_fold(sm, OpMul());
+    nz = wg_fold(sn, OpAdd());
+  }
+  const double Z0 = prod_zero(P0);
+  double* __restrict__ ur = t.park + 4 * t.units + t.ustart[w.s] + w.base;
+  for (i64 l = w.tid; l < w.Kon; l += w.W) {
+    const double u = w.u(l);
+    dr[l] = nz == 0 ? P0 / u : ((nz == 1 && u == 0.0) ? P0 : Z0);
+    if (with_h) ur[l] = u;
+  }
+  if (w.rowon && w.tid == 0) {
+    z[t.zoff[w.s] + w.row] = nz == 0 ? P0 : Z0;
+    if (with_h) t.park[4 * t.start[w.s] + w.row] = nz == 2 ? P0 : Z0;
+  }
+}
+
+// g from the d slots and u from the copy the launch before filled
+__global__ void __launch_bounds__(kBlock) sweep_prod_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
+                                                                 const double* __restrict__ ww) {
+  SpreadEntry en;
+  if (!spread_entry(t, true, en)) return;
+  const i64 s = en.s, base = static_cast<i64>(en.row) * en.K;
+  const double* __restrict__ gr = dv + t.doff[s] + base;
+  const double* __restrict__ ur = t.park + 4 * t.units + t.ustart[s] + base;
+  const double uj = ur[en.j];
+  double h;
+  if (uj != 0.0) h = gr[en.i] / uj;
+  else {
+    const double ui = ur[en.i];
+    h = ui != 0.0 ? gr[en.j] / ui : t.park[4 * t.start[s] + en.row];
+  }
+  hv[t.hoff[s] + en.qa] = ww[t.zoff[s] + en.row] * h;
+}
+
+// ---- quad_over_lin_rows ----
+// A row's Hessian is an arrow of 2K + 1 entries, written by the lanes that hold u_l: no third launch, no packed-index decode.
+//
+// Short rows (K = 2, 3: 32 and 16 rows per wavefront): u^2 through the butterfly, padding lanes carry 0.  Every lane of a
+// group reads the group's y and w (one address per group: the hardware merges them) and writes its g_l, h_ll, h_ly at
+// r K + l -- across the wavefront consecutive addresses in each of the three blocks; lane 0 of the group writes z, g_y,
+// h_yy.  No LDS.
+__global__ void __launch_bounds__(kBlock) sweep_qol_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                           double* __restrict__ z, double* __restrict__ dv,
+                                                           double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  ShortRow w;
+  if (!short_row(t, gidx, x, 0.0, w)) return;
+  const i64 s = w.s, r = w.r, e = w.e, M = w.M;
+  const double u = w.u;
+  double ss = u * u;
+  for (int d = 1; d < w.G; d <<= 1) ss += __shfl_xor(ss, d);
+  if (!w.valid) return;                              // (no exchange between lanes from here on)
+  const i64 a1b = t.a1b[s], MK = M * w.K;
+  const double y = x[a1b >= 0 ? a1b + r : gidx[t.a1o[s] + r]];
+  double* __restrict__ ds = dv + t.doff[s];
+  ds[e] = 2.0 * u / y;
+  if (w.l == 0) {
+    z[t.zoff[s] + r] = ss / y;
+    ds[MK + r] = -ss / (y * y);
+  }
+  if (!with_h) return;
+  const double wr = ww[t.zoff[s] + r];
+  double* __restrict__ hs = hv + t.hoff[s];
+  hs[e] = 2.0 * wr / y;
+  hs[MK + M + e] = -2.0 * wr * u / (y * y);
+  if (w.l == 0) hs[MK + r] = 2.0 * wr * ss / (y * y * y);
+}
+
+// Long rows: partial sums of u^2, then a second lane-strided pass over the row (u re-read: a row of 8 K bytes that the
+// first pass has just brought in) writes g and both Hessian blocks.
+__global__ void __launch_bounds__(kBlock) sweep_qol_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                double* __restrict__ z, double* __restrict__ dv,
+                                                                double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  __shared__ double sm[kBlock / 64];
+  const LongRow w = long_row(t, gidx, x);
+  const i64 s = w.s, row = w.row, K = w.K, M = w.M;
+  double ss = 0.0;
+  for (i64 l = w.tid; l < w.Kon; l += w.W) {
+    const double u = w.u(l);
+    ss += u * u;
+  }
+  ss = wave_all_sum(ss);
+  if (w.wg) ss = wg_combine(sm, w, ss, OpAdd());
+  if (!w.rowon) return;
+  const i64 a1b = t.a1b[s], MK = M * K;
+  const double y = x[a1b >= 0 ? a1b + row : gidx[t.a1o[s] + row]];
+  const double wr = with_h ? ww[t.zoff[s] + row] : 0.0;
+  double* __restrict__ dr = dv + t.doff[s] + w.base;
+  double* __restrict__ hd = hv + t.hoff[s] + w.base;
+  double* __restrict__ hc = hv + t.hoff[s] + MK + M + w.base;
+  for (i64 l = w.tid; l < K; l += w.W) {
+    const double u = w.u(l);
+    dr[l] = 2.0 * u / y;
+    if (with_h) {
+      hd[l] = 2.0 * wr / y;
+      hc[l] = -2.0 * wr * u / (y * y);
+    }
+  }
+  if (w.tid == 0) {
+    z[t.zoff[s] + row] = ss / y;
+    dv[t.doff[s] + MK + row] = -ss / (y * y);
+    if (with_h) hv[t.hoff[s] + MK + row] = 2.0 * wr * ss / (y * y * y);
+  }
+}

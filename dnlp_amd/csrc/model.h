@@ -232,76 +232,74 @@ struct Model {
     }
   }
 
-  // row-class segments (op_is_row): M rows of K entries each.  OP_PROD: sweep_prod_segment below, OP_QUAD_OVER_LIN_ROWS:
-  // sweep_qol_rows_segment.  OP_LOG_SUM_EXP, here:
-  // log_sum_exp over M rows of K entries (lowering.py _lower_log_sum_exp; the reference's
-  // log_sum_exp.py tags the atom smooth and has no _jacobian / _hess_vec to follow).  Per row, with mx = max_l u_l and
-  // e_l = exp(u_l - mx):
-  //   S = sum_l e_l,  r = mx + log S,  p_l = e_l / S,  h_ij = w_r (delta_ij p_i - p_i p_j)   (lower triangle, row-major)
-  // K = 1 gives r = u, p = 1, h = 0 exactly; a row with +inf or NaN gives NaN (inf - inf).  Three maps -- rows, entries,
-  // Hessian entries -- so that the in-kernel space runs every stage with all its lanes; (mx, S) of a row wait in tmpN
-  // between the first two (rows of K >= 2 distinct entries: 2 M <= N, refused otherwise by Tape::load_rows).  The host-driven device space has kernels of
-  // its own (exec_hip.h sweep_rows_*, sweep_prod_* and sweep_qol_*: one set of row tables per opcode).
+  // row-class segments (row_class.h): M rows of K entries each, one rule per member below.  The host-driven device space
+  // has hand-written kernels instead (exec_hip_rows.h), launched over TapeView::row_tab.
   DNLP_HD void sweep_rows(const double* x, bool with_h) {
     DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
     if (t.nrow == 0) return;
     if constexpr (E::is_device && E::has_host_control) {
-      ex->sweep_rows(t.row_short, t.row_long, t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
-      ex->sweep_prod(t.row_prod[0], t.row_prod[1], t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
-      ex->sweep_qol(t.row_qol[0], t.row_qol[1], t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
+      ex->sweep_row_tables(t.row_tab, t.gidx, x, xz + t.N, dvals, hvals, w, with_h);
       return;
     }
     for (i64 rk = 0; rk < t.nrow; ++rk) {
       const SegHost& g = t.segs[t.row_segs[rk]];
-      if (g.op == OP_PROD) { sweep_prod_segment(g, x, with_h); continue; }
-      if (g.op == OP_QUAD_OVER_LIN_ROWS) { sweep_qol_rows_segment(g, x, with_h); continue; }
-      if (g.op != OP_LOG_SUM_EXP) DNLP_FAIL("row-class segment with an unknown opcode");
-      const i32* gidx = t.gidx;
-      const i64 M = g.d0, K = g.d1, T = K * (K + 1) / 2, a0b = g.a0_base, a0o = g.a0_off;
-      double* z = xz + t.N + g.zoff;
-      double* dv = dvals + g.doff;
-      double* hv = hvals + g.hoff;
-      const double* ww = w + g.zoff;
-      if (K == 1) {
-        // r = u, p = 1, h = 0 exactly for a finite u; through the same expressions as longer rows, so that +-inf and NaN
-        // give NaN here as they do there (exp(u - u)) and in the device kernels
-        ex->map(M, [=] DNLP_HD(i64 r) {
-          const double u = x[a0b >= 0 ? a0b + r : gidx[a0o + r]];
-          const double ev = exp(u - u), p = ev / ev;
-          z[r] = u + log(ev);
-          dv[r] = p;
-          if (with_h) hv[r] = ww[r] * (p - p * p);
-        });
-        continue;
-      }
-      // (2 M <= N for these rows is checked where the tape is loaded: Tape::load_rows)
-      double* ms = tmpN;
-      ex->map(M, [=] DNLP_HD(i64 r) {
-        const i64 b = r * K;
-        double mx = -kInf;
-        for (i64 l = 0; l < K; ++l) { const double u = x[a0b >= 0 ? a0b + b + l : gidx[a0o + b + l]]; if (u > mx) mx = u; }
-        double S = 0.0;
-        for (i64 l = 0; l < K; ++l) S += exp(x[a0b >= 0 ? a0b + b + l : gidx[a0o + b + l]] - mx);
-        z[r] = mx + log(S);
-        ms[2 * r] = mx;
-        ms[2 * r + 1] = S;
-      });
-      ex->map(M * K, [=] DNLP_HD(i64 e) {
-        const i64 r = e / K;
-        dv[e] = exp(x[a0b >= 0 ? a0b + e : gidx[a0o + e]] - ms[2 * r]) / ms[2 * r + 1];
-      });
-      if (!with_h) continue;
-      ex->map(M * T, [=] DNLP_HD(i64 e) {
-        const i64 r = e / T, q = e - r * T;
-        // tril_indices order: row-major over the lower triangle (as hess_coo below)
-        i64 i = static_cast<i64>((sqrt(8.0 * static_cast<double>(q) + 1.0) - 1.0) * 0.5);
-        while (i * (i + 1) / 2 > q) --i;
-        while ((i + 1) * (i + 2) / 2 <= q) ++i;
-        const i64 j = q - i * (i + 1) / 2;
-        const double pi = dv[r * K + i], pj = dv[r * K + j];
-        hv[e] = ww[r] * (i == j ? pi - pi * pj : -(pi * pj));
-      });
+      if (g.op == OP_LOG_SUM_EXP) sweep_lse_segment(g, x, with_h);
+      else if (g.op == OP_PROD) sweep_prod_segment(g, x, with_h);
+      else if (g.op == OP_QUAD_OVER_LIN_ROWS) sweep_qol_rows_segment(g, x, with_h);
+      else DNLP_FAIL("row-class segment with an unknown opcode");
     }
+  }
+
+  // OP_LOG_SUM_EXP (lowering.py _lower_log_sum_exp; the reference's log_sum_exp.py tags the atom smooth and has no
+  // _jacobian / _hess_vec to follow).  Per row, with mx = max_l u_l and e_l = exp(u_l - mx):
+  //   S = sum_l e_l,  r = mx + log S,  p_l = e_l / S,  h_ij = w_r (delta_ij p_i - p_i p_j)   (lower triangle, row-major)
+  // K = 1 gives r = u, p = 1, h = 0 exactly; a row with +inf or NaN gives NaN (inf - inf).  Three maps -- rows, entries,
+  // Hessian entries -- so that the in-kernel space runs every stage with all its lanes; (mx, S) of a row wait in tmpN
+  // between the first two (rows of K >= 2 distinct entries: 2 M <= N, refused otherwise by Tape::load_rows).
+  DNLP_HD void sweep_lse_segment(const SegHost& g, const double* x, bool with_h) {
+    DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
+    const i32* gidx = t.gidx;
+    const i64 M = g.d0, K = g.d1, T = K * (K + 1) / 2, a0b = g.a0_base, a0o = g.a0_off;
+    double* z = xz + t.N + g.zoff;
+    double* dv = dvals + g.doff;
+    double* hv = hvals + g.hoff;
+    const double* ww = w + g.zoff;
+    if (K == 1) {
+      // r = u, p = 1, h = 0 exactly for a finite u; through the same expressions as longer rows, so that +-inf and NaN
+      // give NaN here as they do there (exp(u - u)) and in the device kernels
+      ex->map(M, [=] DNLP_HD(i64 r) {
+        const double u = x[arg_at(a0b, a0o, gidx, r)];
+        const double ev = exp(u - u), p = ev / ev;
+        z[r] = u + log(ev);
+        dv[r] = p;
+        if (with_h) hv[r] = ww[r] * (p - p * p);
+      });
+      return;
+    }
+    // (2 M <= N for these rows is checked where the tape is loaded: Tape::load_rows)
+    double* ms = tmpN;
+    ex->map(M, [=] DNLP_HD(i64 r) {
+      const i64 b = r * K;
+      double mx = -kInf;
+      for (i64 l = 0; l < K; ++l) { const double u = x[arg_at(a0b, a0o, gidx, b + l)]; if (u > mx) mx = u; }
+      double S = 0.0;
+      for (i64 l = 0; l < K; ++l) S += exp(x[arg_at(a0b, a0o, gidx, b + l)] - mx);
+      z[r] = mx + log(S);
+      ms[2 * r] = mx;
+      ms[2 * r + 1] = S;
+    });
+    ex->map(M * K, [=] DNLP_HD(i64 e) {
+      const i64 r = e / K;
+      dv[e] = exp(x[arg_at(a0b, a0o, gidx, e)] - ms[2 * r]) / ms[2 * r + 1];
+    });
+    if (!with_h) return;
+    ex->map(M * T, [=] DNLP_HD(i64 e) {
+      const i64 r = e / T;
+      i64 i, j;
+      tri_decode(e - r * T, false, i, j);
+      const double pi = dv[r * K + i], pj = dv[r * K + j];
+      hv[e] = ww[r] * (i == j ? pi - pi * pj : -(pi * pj));
+    });
   }
 
   // OP_PROD (lowering.py _lower_Prod; the reference's prod.py has no derivative rule to follow).  Per row u of length K,
@@ -312,8 +310,8 @@ struct Model {
   //   h_ij = w_r * (u_j != 0 ? g_i / u_j : u_i != 0 ? g_j / u_i : (nz == 2 ? P0 : Z0))        (i > j: the strict triangle)
   // No division by zero; exact with one, two or more zeros in a row.  A NaN entry makes P0 NaN and with it the value,
   // every g and every h of the row (Z0 carries it past a zero).  +-inf is a nonzero entry: it enters P0 (a row with an
-  // infinite entry and a zero has value 0), and the derivative by that entry is inf / inf = NaN.  Three maps as above;
-  // (P0, nz) of a row wait in tmpN between them.
+  // infinite entry and a zero has value 0), and the derivative by that entry is inf / inf = NaN.  Three maps as for
+  // log_sum_exp; (P0, nz) of a row wait in tmpN between them.
   DNLP_HD void sweep_prod_segment(const SegHost& g, const double* x, bool with_h) {
     DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
     const i32* gidx = t.gidx;
@@ -326,7 +324,7 @@ struct Model {
       // z = u, g = 1, no Hessian entry; through the rule's own expressions (u / u), so that +-inf and NaN give what they
       // give in longer rows and in the device kernels; nothing is parked (2 M <= N need not hold)
       ex->map(M, [=] DNLP_HD(i64 r) {
-        const double u = x[a0b >= 0 ? a0b + r : gidx[a0o + r]];
+        const double u = x[arg_at(a0b, a0o, gidx, r)];
         z[r] = u;
         dv[r] = u == 0.0 ? 1.0 : u / u;
       });
@@ -339,7 +337,7 @@ struct Model {
       double P0 = 1.0;
       i64 nz = 0;
       for (i64 l = 0; l < K; ++l) {
-        const double u = x[a0b >= 0 ? a0b + b + l : gidx[a0o + b + l]];
+        const double u = x[arg_at(a0b, a0o, gidx, b + l)];
         if (u == 0.0) ++nz; else P0 *= u;
       }
       z[r] = nz == 0 ? P0 : (P0 != P0 ? P0 : 0.0);
@@ -348,20 +346,15 @@ struct Model {
     });
     ex->map(M * K, [=] DNLP_HD(i64 e) {
       const i64 r = e / K;
-      const double u = x[a0b >= 0 ? a0b + e : gidx[a0o + e]], P0 = pk[2 * r], nz = pk[2 * r + 1];
+      const double u = x[arg_at(a0b, a0o, gidx, e)], P0 = pk[2 * r], nz = pk[2 * r + 1];
       dv[e] = nz == 0.0 ? P0 / u : ((nz == 1.0 && u == 0.0) ? P0 : (P0 != P0 ? P0 : 0.0));
     });
     if (!with_h) return;
     ex->map(M * T, [=] DNLP_HD(i64 e) {
-      const i64 r = e / T, q = e - r * T;
-      // tril_indices(K, -1) order: entry q of the strict triangle is entry q of the full one a row further down
-      i64 i = static_cast<i64>((sqrt(8.0 * static_cast<double>(q) + 1.0) - 1.0) * 0.5);
-      while (i * (i + 1) / 2 > q) --i;
-      while ((i + 1) * (i + 2) / 2 <= q) ++i;
-      const i64 j = q - i * (i + 1) / 2;
-      ++i;
-      const i64 b = r * K;
-      const double ui = x[a0b >= 0 ? a0b + b + i : gidx[a0o + b + i]], uj = x[a0b >= 0 ? a0b + b + j : gidx[a0o + b + j]];
+      const i64 r = e / T, b = r * K;
+      i64 i, j;
+      tri_decode(e - r * T, true, i, j);      // (tril_indices(K, -1) order)
+      const double ui = x[arg_at(a0b, a0o, gidx, b + i)], uj = x[arg_at(a0b, a0o, gidx, b + j)];
       const double P0 = pk[2 * r];
       double h;
       if (uj != 0.0) h = dv[b + i] / uj;
@@ -390,16 +383,16 @@ struct Model {
     ex->map(M, [=] DNLP_HD(i64 r) {
       const i64 b = r * K;
       double ss = 0.0;
-      for (i64 l = 0; l < K; ++l) { const double u = x[a0b >= 0 ? a0b + b + l : gidx[a0o + b + l]]; ss += u * u; }
-      const double y = x[a1b >= 0 ? a1b + r : gidx[a1o + r]];
+      for (i64 l = 0; l < K; ++l) { const double u = x[arg_at(a0b, a0o, gidx, b + l)]; ss += u * u; }
+      const double y = x[arg_at(a1b, a1o, gidx, r)];
       z[r] = ss / y;
       dv[M * K + r] = -ss / (y * y);
       if (with_h) hv[M * K + r] = 2.0 * ww[r] * ss / (y * y * y);
     });
     ex->map(M * K, [=] DNLP_HD(i64 e) {
       const i64 r = e / K;
-      const double y = x[a1b >= 0 ? a1b + r : gidx[a1o + r]];
-      const double u = x[a0b >= 0 ? a0b + e : gidx[a0o + e]];
+      const double y = x[arg_at(a1b, a1o, gidx, r)];
+      const double u = x[arg_at(a0b, a0o, gidx, e)];
       dv[e] = 2.0 * u / y;
       if (with_h) {
         const double wz = ww[r];

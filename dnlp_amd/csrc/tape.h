@@ -12,6 +12,7 @@
 
 #include "atom_math.h"     // (op_is_row)
 #include "exec.h"
+#include "row_class.h"     // (RowTable, the table of row-class members)
 #include "wave_hdr.h"      // (kCooHeavy)
 
 namespace dnlp {
@@ -135,32 +136,6 @@ struct DenseBlock {
 
 struct SparseConst { Csr P, PT; i64 nh = 0; double* hv = nullptr; };
 
-// Row-class segments (atom_math.h op_is_row) as the device sweep walks them (exec_hip.h sweep_rows_* / sweep_prod_* / sweep_qol_*): one
-// table row per segment, exec space, and ONE TABLE PER OPCODE AND KERNEL FORM -- a table has no opcode column, every
-// kernel serves one opcode.  `start` is the prefix of launch work (wavefronts for the short-row form, workgroups for the
-// long-row forms), `hstart` the prefix of Hessian entries (M row_hcount(op, K) per segment).  `park` (OP_PROD, long rows):
-// what waits for the Hessian launch (exec_hip.h) -- one double per row slot 4 start[s] + row for the row's product, then,
-// from 4 units on, a contiguous copy of every row's entries at ustart[s] + row K (`ustart`: the prefix of M K).
-struct RowTable {
-  i64 n = 0, units = 0, hunits = 0;
-  i64 *start = nullptr, *hstart = nullptr;
-  i64 *K = nullptr, *M = nullptr, *a0b = nullptr, *a0o = nullptr, *zoff = nullptr, *doff = nullptr, *hoff = nullptr;
-  double* park = nullptr;
-  i64* ustart = nullptr;
-  i64 *a1b = nullptr, *a1o = nullptr;      // OP_QUAD_OVER_LIN_ROWS: the second argument (one entry per row), as a0b / a0o
-};
-// K <= kRowShortMax: a row is a power-of-two group of lanes inside one wavefront.  Above: one wavefront per row up to
-// kRowWaveMax entries (32 serial entries per lane), one 256-lane workgroup per row beyond.  The switch points are recorded
-// with the measured shapes in profiles/log_sum_exp_sweep.jsonl; other values of kRowWaveMax have not been measured.
-// packed Hessian entries of one row of K entries: the lower triangle with (log_sum_exp) or without (prod) its diagonal
-inline i64 row_tri(int op, i64 K) { return op == OP_PROD ? K * (K - 1) / 2 : K * (K + 1) / 2; }
-// Hessian and first-derivative entries of one row: OP_QUAD_OVER_LIN_ROWS has no triangle but an arrow -- K diagonal
-// entries, the denominator's, K cross entries -- and one more first derivative (by the denominator)
-inline i64 row_hcount(int op, i64 K) { return op == OP_QUAD_OVER_LIN_ROWS ? 2 * K + 1 : row_tri(op, K); }
-inline i64 row_dcount(int op, i64 K) { return op == OP_QUAD_OVER_LIN_ROWS ? K + 1 : K; }
-constexpr i64 kRowShortMax = 64;
-constexpr i64 kRowWaveMax = 2048;
-
 // Index of a COO pattern BY OUTPUT, built once when the tape is loaded: the entries that feed output g are the
 // segment ptr[g] .. ptr[g+1] of (ent = COO entry, src = index into the multiplied vector), in storage order.
 // A product that walks the segments sums every output in one fixed order: no floating-point atomics, the same
@@ -215,9 +190,9 @@ struct TapeView {
   i64 nred = 0;
   const i64* row_segs = nullptr;        // row-class segments (op_is_row), control space
   i64 nrow = 0;
-  RowTable row_short, row_long;         // the OP_LOG_SUM_EXP segments by kernel form, exec space (device sweep)
-  const RowTable* row_prod = nullptr;   // [2], control space: the OP_PROD segments, short and long form
-  const RowTable* row_qol = nullptr;    // [2], control space: the OP_QUAD_OVER_LIN_ROWS segments, short and long form
+  // control space, [kRowMembers][kRowForms] (row_class.h): the row-class segments by member and kernel form, read by
+  // the host when it launches the device sweep (the tables' arrays are in exec space)
+  const RowTable* row_tab = nullptr;
   const double** dense_ptr = nullptr;   // per dense constant: exec-space column-major matrix (or null until bound)
   i64* dense_ld = nullptr;
   const SparseConst* sparse = nullptr;
@@ -241,8 +216,7 @@ struct Tape : TapeView {
   std::vector<SegHost> h_segs;
   std::vector<i64> h_red_segs;   // indices of reduction-class segments
   std::vector<i64> h_row_segs;   // indices of row-class segments
-  std::vector<RowTable> h_row_prod;   // TapeView::row_prod
-  std::vector<RowTable> h_row_qol;    // TapeView::row_qol
+  std::vector<RowTable> h_row_tab;    // TapeView::row_tab
   std::vector<i64> h_flat_seg;   // segment index of every flat-table row
   std::vector<i32> h_jac_rows, h_jac_cols, h_hess_rows, h_hess_cols;
   std::vector<double> h_jac_const;   // |coefficient| of Jacobian entries that are constant (affine rows), else 0
@@ -451,30 +425,20 @@ struct Tape : TapeView {
     load_reduction(tb);
   }
 
-  // the row-class segments split by opcode and kernel form, with their prefixes of launch work
+  // the row-class segments split by member (row_class.h) and kernel form, with their prefixes of launch work
   void load_rows() {
-    h_row_prod.assign(2, RowTable{});
-    h_row_qol.assign(2, RowTable{});
-    // one entry per member of the class: its name in messages, its two tables (short, long form), whether the generic
-    // sweep parks two numbers per row in an N-vector (model.h), whether it has a second argument, and whether its long
-    // rows' Hessian entries are written by a spread launch of their own that walks `hstart`
-    struct Member { int op; const char* name; RowTable* tab[2]; bool parks, two_args, spread_hess; };
-    const Member members[] = {
-      {OP_LOG_SUM_EXP, "log_sum_exp", {&row_short, &row_long}, true, false, true},
-      {OP_PROD, "prod", {&h_row_prod[0], &h_row_prod[1]}, true, false, true},
-      {OP_QUAD_OVER_LIN_ROWS, "quad_over_lin_rows", {&h_row_qol[0], &h_row_qol[1]}, false, true, false},
-    };
-    for (const Member& mb : members)
-    for (int lng = 0; lng < 2; ++lng) {
-      const int op = mb.op;
+    h_row_tab.assign(kRowMembers * kRowForms, RowTable{});
+    for (int k = 0; k < kRowMembers; ++k)
+    for (int lng = 0; lng < kRowForms; ++lng) {
+      const RowMember mb = row_member(k);
       std::vector<i64> st{0}, hs{0}, us{0}, K, M, a0b, a0o, a1b, a1o, zo, dof, ho;
       for (i64 s : h_row_segs) {
         const SegHost& g = h_segs[static_cast<size_t>(s)];
-        if (g.op != op) continue;
+        if (g.op != mb.op) continue;
         const std::string name = mb.name;
         const i64 rows = g.d0, len = g.d1;
-        if (rows <= 0 || len <= 0 || g.a0_len != rows * len || g.zcount != rows || g.dcount != rows * row_dcount(op, len) ||
-            g.hcount != rows * row_hcount(op, len) || (mb.two_args && g.a1_len != rows))
+        if (rows <= 0 || len <= 0 || g.a0_len != rows * len || g.zcount != rows || g.dcount != rows * mb.row_dcount(len) ||
+            g.hcount != rows * mb.row_hcount(len) || (mb.two_args && g.a1_len != rows))
           throw std::runtime_error(name + " segment with inconsistent counts");
         // rows that share entries across rows could outnumber the N-vector the generic sweep parks in.  The front-end
         // cannot produce such a tape (the argument is one variable).
@@ -490,7 +454,7 @@ struct Tape : TapeView {
         a1b.push_back(g.a1_base); a1o.push_back(g.a1_off);
         zo.push_back(g.zoff); dof.push_back(g.doff); ho.push_back(g.hoff);
       }
-      RowTable& rt = *mb.tab[lng];
+      RowTable& rt = h_row_tab[static_cast<size_t>(k * kRowForms + lng)];
       rt.n = static_cast<i64>(K.size());
       rt.units = st.back(); rt.hunits = lng ? hs.back() : 0;
       if (rt.n == 0) continue;
@@ -500,13 +464,12 @@ struct Tape : TapeView {
       rt.a0b = up(a0b.data(), a0b.size()); rt.a0o = up(a0o.data(), a0o.size());
       rt.zoff = up(zo.data(), zo.size()); rt.doff = up(dof.data(), dof.size()); rt.hoff = up(ho.data(), ho.size());
       if (mb.two_args) { rt.a1b = up(a1b.data(), a1b.size()); rt.a1o = up(a1o.data(), a1o.size()); }
-      if (op == OP_PROD && lng) {
+      if (mb.op == OP_PROD && lng) {
         rt.ustart = up(us.data(), us.size());
         rt.park = ex->template alloc<double>(static_cast<size_t>(4 * rt.units + us.back()));
       }
     }
-    row_prod = h_row_prod.data();
-    row_qol = h_row_qol.data();
+    row_tab = h_row_tab.data();
   }
 
   void load_reduction(const TapeBlob& tb) {

@@ -1,4 +1,4 @@
-"""log_sum_exp on the device: the row-class kernels (csrc/exec_hip.h sweep_rows_kernel / sweep_rows_long_kernel /
+"""log_sum_exp on the device: the row-class kernels (csrc/exec_hip_rows.h sweep_rows_kernel / sweep_rows_long_kernel /
 sweep_rows_hess_kernel) entry by entry against mpmath with the bounds of tests/lse_reference.py, on the tapes of the CPU
 tests and on row shapes that reach every kernel form and its edges; bit-for-bit repeats; the three solves of
 tests/lse_problems.py through the front-end on every solver path; softmax regression at a user's size; the geometric program

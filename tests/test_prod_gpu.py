@@ -1,4 +1,4 @@
-"""prod on the device: the row-class kernels of OP_PROD (csrc/exec_hip.h sweep_prod_kernel / sweep_prod_long_kernel /
+"""prod on the device: the row-class kernels of OP_PROD (csrc/exec_hip_rows.h sweep_prod_kernel / sweep_prod_long_kernel /
 sweep_prod_hess_kernel) entry by entry against mpmath within the derived bound of tests/prod_reference.py, on the tapes
 of the CPU tests and on row shapes that reach every kernel form and its edges; zeros in every form; bit-for-bit repeats;
 the solves of tests/prod_problems.py through the front-end on every solver path; the box volume as a batch template."""

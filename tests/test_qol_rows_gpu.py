@@ -1,4 +1,4 @@
-"""Row-wise 2-norms on the device: the row-class kernels of OP_QUAD_OVER_LIN_ROWS (csrc/exec_hip.h sweep_qol_kernel /
+"""Row-wise 2-norms on the device: the row-class kernels of OP_QUAD_OVER_LIN_ROWS (csrc/exec_hip_rows.h sweep_qol_kernel /
 sweep_qol_long_kernel) entry by entry against mpmath within the derived bound of tests/qol_rows_reference.py, on the
 tapes of the CPU tests and on row shapes that reach every kernel form and both sides of each switch; bit-for-bit repeats;
 the solves of tests/qol_rows_problems.py through the front-end on every solver path; Fermat-Weber as a batch template."""
@@ -124,6 +124,45 @@ def test_mixed_tape(gpu_required):
     ra, rb = rows_of_other_atoms(a, {36}), rows_of_other_atoms(b, set())
     assert ra.size == rb.size == 50 + 1 + 3 + 9 + 4
     assert ga[ra].tobytes() == gb[rb].tobytes()
+
+
+def test_mixed_tape_fills_all_six_row_tables(gpu_required):
+    """All three members of the row class in both kernel forms in one tape -- log_sum_exp 3 x 5 and 2 x 70, prod 4 x 3 and
+    2 x 66, quad_over_lin_rows 6 x 5, 2 x 70 and 1 x 2049 (the workgroup form) -- so that one sweep walks six non-empty row
+    tables; an elementwise segment between the short and the long blocks, non-zero multipliers on every row.  Every
+    row-class segment against its own mpmath reference within that atom's bound; two evaluations give the same bytes."""
+    from test_log_sum_exp_gpu import _check_segment_mpmath as check_lse
+    from test_prod_gpu import _check_rows_mpmath as check_prod
+    qol_sets = [qr.rows_of_shape(6, 5, seed=61), qr.rows_of_shape(2, 70, seed=62), qr.rows_of_shape(1, 2049, seed=63)]
+    rng = np.random.default_rng(9)
+    u, v = cp.Variable(50), cp.Variable(9)
+    u.value, v.value = rng.standard_normal(50), rng.uniform(0.5, 2, 9)
+    Ls, Ll, Ps, Pl = cp.Variable((3, 5)), cp.Variable((2, 70)), cp.Variable((4, 3)), cp.Variable((2, 66))
+    Ls.value, Ll.value = lr.rows_of_length(5, 3, seed=64), lr.rows_of_length(70, 2, seed=65)
+    Ps.value, Pl.value = pr.rows_of_length(3, 4, seed=66), pr.rows_of_length(66, 2, seed=67)
+    Qs, ys, Ql, yl, Qw, yw = cp.Variable((6, 5)), cp.Variable(6), cp.Variable((2, 70)), cp.Variable(2), cp.Variable(2049), cp.Variable()
+    (Qs.value, ys.value), (Ql.value, yl.value) = qol_sets[0], qol_sets[1]
+    Qw.value, yw.value = qol_sets[2][0][0], qol_sets[2][1][0]
+    cons = [cp.exp(u) <= 3, cp.log_sum_exp(Ls, axis=1) <= 0, cp.prod(Ps, axis=1) <= 0, cp.quad_over_lin_rows(Qs, ys, axis=1) <= 0,
+            cp.sin(v) >= -1, cp.log_sum_exp(Ll, axis=1) <= 0, cp.prod(Pl, axis=1) <= 0, cp.quad_over_lin_rows(Ql, yl, axis=1) <= 0,
+            cp.quad_over_lin_rows(Qw, yw) <= 0]
+    data = lp.lower(cp.Problem(cp.Minimize(cp.sum(cp.exp(u))), cons))
+    a, x = data["tape_arrays"], np.array(data["x0"], dtype=float)
+    assert list(a["seg_op"]) == [1, 1, 34, 35, 36, 6, 34, 35, 36, 36]
+    assert [(int(a["seg_d0"][s]), int(a["seg_d1"][s])) for s in (2, 3, 4, 6, 7, 8, 9)] == [(3, 5), (4, 3), (6, 5), (2, 70), (2, 66), (2, 70), (1, 2049)]
+    lam = lp.multipliers(int(a["dims"][1]))
+    dev = _device(a)
+    try:
+        g, J, H = dev.eval_g(x), dev.eval_jac_g(x), dev.eval_h(x, lam, 0.5)
+        assert (dev.eval_g(x).tobytes(), dev.eval_jac_g(x).tobytes(), dev.eval_h(x, lam, 0.5).tobytes()) == (g.tobytes(), J.tobytes(), H.tobytes())
+        for s in (2, 6):
+            print("six tables, log_sum_exp segment %d: worst error %.3f of its bound" % (s, check_lse(a, x, lam, g, J, H, s, np.arange(int(a["seg_d0"][s])))))
+        for s in (3, 7):
+            print("six tables, prod segment %d: worst error %.3f of its bound" % (s, check_prod(a, x, lam, g, J, H, s, np.arange(int(a["seg_d0"][s])))))
+        for s in (4, 8, 9):
+            print("six tables, quad_over_lin_rows segment %d: worst error %.3f of its bound" % (s, qr.check_segment("six tables", dev, (a, x, lam, 0.5), s)))
+    finally:
+        dev.close()
 
 
 def test_first_derivatives_do_not_depend_on_the_hessian_pass(gpu_required):
