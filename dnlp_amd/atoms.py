@@ -703,6 +703,54 @@ class xexp(_Unary):
         return (self.args[0].is_nonneg(), self.args[0].is_nonpos())
 
 
+_RT_HALF = np.sqrt(0.5)
+
+
+class log_normcdf(_Unary):
+    """log Phi(x), Phi the standard normal CDF: exact, with derivatives, where the reference's atom of this name
+    (atoms/elementwise/log_normcdf.py) is a quadratic DCP fit good to two digits and has no rule on the NLP path.
+    Concave, increasing, non-positive, no domain; tape op 14 (csrc/atom_math.h log_normcdf_rules, whose formulas
+    `numeric` restates through the scaled complementary error function E(t) = exp(t^2) erfc(t))."""
+    CONCAVE, INCR = True, True
+
+    def numeric(self, values):
+        u = np.asarray(values[0], dtype=float)
+        neg, pos = np.minimum(u, 0.0), np.maximum(u, 0.0)
+        with np.errstate(all="ignore"):
+            left = np.log(0.5 * special.erfcx(-neg * _RT_HALF)) - 0.5 * neg * neg
+            right = np.log1p(-0.5 * np.exp(-0.5 * pos * pos) * special.erfcx(pos * _RT_HALF))
+        return np.where(u <= 0, left, np.where(u > 0, right, u))
+
+    def sign_from_args(self):
+        return (False, True)
+
+
+class normcdf(_Unary):
+    """Phi(x): neither convex nor concave, increasing, non-negative, smooth everywhere (ESR and HSR like sin); the
+    reference has no such atom.  Tape op 15; both tails from the same E, so Phi(-37) keeps its relative accuracy."""
+    INCR = True
+
+    def numeric(self, values):
+        u = np.asarray(values[0], dtype=float)
+        with np.errstate(all="ignore"):
+            tail = 0.5 * np.exp(-0.5 * u * u) * special.erfcx(np.abs(u) * _RT_HALF)
+        return np.where(u <= 0, tail, 1.0 - tail)
+
+    def sign_from_args(self):
+        return (True, False)
+
+
+class loggamma(_Unary):
+    """ln Gamma(x), domain x > 0: exact, with digamma and trigamma as derivatives, where the reference's loggamma.py is
+    a piecewise DCP approximation.  Convex, not monotone, sign unknown; tape op 16."""
+    CONVEX = True
+
+    def numeric(self, values):
+        u = np.asarray(values[0], dtype=float)
+        with np.errstate(all="ignore"):
+            return np.where(u >= 0, special.gammaln(np.maximum(u, 0.0)), np.nan)
+
+
 class sin(_Unary):
     """sin x (reference atoms/elementwise/trig.py:25-105)."""
 

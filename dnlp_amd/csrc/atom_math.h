@@ -10,6 +10,7 @@ namespace dnlp {
 enum Op : int {
   OP_EXP = 1, OP_LOG = 2, OP_ENTR = 3, OP_LOGISTIC = 4, OP_POWER = 5, OP_SIN = 6, OP_COS = 7,
   OP_TAN = 8, OP_SINH = 9, OP_TANH = 10, OP_ASINH = 11, OP_ATANH = 12, OP_XEXP = 13,
+  OP_LOG_NORMCDF = 14, OP_NORMCDF = 15, OP_LOGGAMMA = 16,     // no reference rule: exact smooth atoms
   OP_MUL = 20, OP_REL_ENTR = 21,
   OP_QUAD_FORM_DENSE = 30, OP_QUAD_FORM_SPARSE = 31, OP_QUAD_OVER_LIN = 32, OP_MATMUL = 33,
   OP_LOG_SUM_EXP = 34,     // row class (model.h sweep_rows): M rows of K entries, one dense K x K Hessian block per row
@@ -34,6 +35,132 @@ DNLP_HD inline double pow_fast(double u, double p) {
   if (p == -1.5) return 1.0 / (u * sqrt(u));
   if (p == 4.0) { double t = u * u; return t * t; }
   return pow(u, p);
+}
+
+// ---- special functions of the statistical atoms (log_normcdf, normcdf, loggamma) ---------------------------------------------
+// One text for the host build, the tape kernels and the kernels compiled at run time.  Everything is straight-line
+// arithmetic on literals: no table is read from memory.
+// The three rules are functions of their own on the device: inlined into unary_rules they cost kernels that never meet them
+// registers (batch_solve_kernel<64> spilled 32 more VGPRs, the fused kernels three times their scratch); see DESIGN.md section 2.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DNLP_OUTLINE __attribute__((noinline))
+#else
+#define DNLP_OUTLINE
+#endif
+struct Rule3 { double val, d1, d2; };      // returned by value: in registers (reference arguments of a called function live in scratch)
+
+// E(t) = exp(t^2) erfc(t) for t >= 0, the scaled complementary error function.  q = (t - 4) / (t + 4) maps [0, inf) to
+// [-1, 1), where (1 + 2 t) E(t) is a smooth function between 1 and 2 / sqrt(pi): 1 + a polynomial of degree 26 in q (the
+// Chebyshev interpolant at 80 points, cut where its coefficients fall below 2^-60, in the monomial basis; sum |a_k| = 0.78, so
+// Horner's rounding stays below one unit of the leading 1).  No exp is taken, so nothing overflows; at t -> 0 the result is
+// 1 - 1.128 t with the rounding of 1, at t -> inf it is 1 / (t sqrt(pi)).  Worst error against mpmath: 1.6 ulp.
+DNLP_HD inline double erfcx_nonneg(double t) {
+  if (!(t < 1.152921504606846976e18)) return t != t ? t : 0.56418958354775629 / t;      // 1 + 2 t stays finite below; E = 1 / (t sqrt(pi)) to the last bit here
+  const double m = t - 4.0, r = 1.0 / (t + 4.0);
+  double q = m * r;
+  q = fma(r, fma(q, -t, fma(q + 1.0, -4.0, t)), q);                    // one Newton step: q is (t - 4) / (t + 4) to half an ulp
+  double p = 4.1808217396755443e-11;
+  p = p * q - 1.3746529890011639e-10;
+  p = p * q - 5.3771338210317935e-10;
+  p = p * q + 1.7903326159489847e-09;
+  p = p * q + 3.9508792541666846e-09;
+  p = p * q - 1.4709550868669278e-08;
+  p = p * q - 2.1868462576141457e-08;
+  p = p * q + 1.1009737295274889e-07;
+  p = p * q + 7.888177117406594e-08;
+  p = p * q - 8.2491984275083543e-07;
+  p = p * q + 2.9094470866632674e-07;
+  p = p * q + 5.7092060530721826e-06;
+  p = p * q - 1.1220772697788498e-05;
+  p = p * q - 2.4398944545280832e-05;
+  p = p * q + 0.00015062131406268513;
+  p = p * q - 0.00019925677576336479;
+  p = p * q - 0.00075777322105128491;
+  p = p * q + 0.0050319699926699331;
+  p = p * q - 0.016197734065728945;
+  p = p * q + 0.037167515535929112;
+  p = p * q - 0.066330365811668124;
+  p = p * q + 0.093732834998438264;
+  p = p * q - 0.10103906603632413;
+  p = p * q + 0.068097054254690398;
+  p = p * q + 0.015379652102620026;
+  p = p * q - 0.1396211168405625;
+  p = p * q + 0.2329951186255525;
+  return (p + 1.0) / (1.0 + 2.0 * t);
+}
+
+// exp(-u^2 / 2) with the rounding of u^2 put back (u^2 = s + lo exactly): full relative accuracy where s / 2 is in the
+// hundreds.  Zero from |u| = 40 on (exp(-800) is below the smallest subnormal); NaN stays NaN.
+DNLP_HD inline double exp_neg_half_square(double u) {
+  const double s = u * u;
+  if (!(s < 1600.0)) return s != s ? s : 0.0;
+  const double g = exp(-0.5 * s);
+  return fma(-0.5 * fma(u, u, -s), g, g);
+}
+
+// digamma psi(u) and trigamma psi_1(u) for u > 0: psi(u) = psi(u + 1) - 1 / u and psi_1(u) = psi_1(u + 1) + 1 / u^2 upward until
+// the argument reaches 10 (at most ten steps), there the asymptotic series in 1 / x^2 with the Bernoulli numbers up to B_16
+// (psi; the first term left out is 3e-18) and B_18 (psi_1; 5e-19 of psi_1(10) = 0.105).
+DNLP_HD inline void digamma_trigamma(double u, double& psi, double& psi1) {
+  double x = u, s0 = 0.0, s1 = 0.0;
+  while (x < 10.0) {
+    const double r = 1.0 / x;
+    s0 += r; s1 += r * r; x += 1.0;
+  }
+  const double r = 1.0 / x, w = r * r;
+  double a = 3617.0 / 8160.0;                      // B_2k / (2 k), k = 8 .. 1
+  a = a * w - 1.0 / 12.0;
+  a = a * w + 691.0 / 32760.0;
+  a = a * w - 1.0 / 132.0;
+  a = a * w + 1.0 / 240.0;
+  a = a * w - 1.0 / 252.0;
+  a = a * w + 1.0 / 120.0;
+  a = a * w - 1.0 / 12.0;
+  psi = (log(x) - 0.5 * r + a * w) - s0;
+  double b = 43867.0 / 798.0;                      // B_2k, k = 9 .. 1
+  b = b * w - 3617.0 / 510.0;
+  b = b * w + 7.0 / 6.0;
+  b = b * w - 691.0 / 2730.0;
+  b = b * w + 5.0 / 66.0;
+  b = b * w - 1.0 / 30.0;
+  b = b * w + 1.0 / 42.0;
+  b = b * w - 1.0 / 30.0;
+  b = b * w + 1.0 / 6.0;
+  psi1 = (r + 0.5 * w + b * w * r) + s1;
+}
+
+// log Phi(u), lambda = phi / Phi, -lambda (u + lambda), through E alone: Phi(u) and 1 - Phi(u) never exist as rounded doubles where
+// they cancel or underflow.
+DNLP_OUTLINE DNLP_HD inline Rule3 log_normcdf_rules(double u) {
+  double val, d1, d2;
+  const double kRtHalf = 0.70710678118654752, kRt2OverPi = 0.79788456080286536;
+  if (u <= 0.0) {
+    const double E = erfcx_nonneg(-u * kRtHalf), lam = kRt2OverPi / E;
+    val = log(0.5 * E) - 0.5 * u * u; d1 = lam;
+    // lambda = -u - 1 / u + 2 / u^3 - ...: u + lambda is the difference of two numbers u^2 times its size, and beyond -2^26 nothing
+    // of it is left.  From -128 on the product's own series in w = 1 / u^2 takes over (the first term left out, 6354 w^5, is
+    // below 2^-57 there; the expression itself has lost 14 bits by then)
+    if (u > -128.0) d2 = -lam * (u + lam);
+    else { const double w = 1.0 / (u * u); d2 = (((-518.0 * w + 50.0) * w - 6.0) * w + 1.0) * w - 1.0; }
+  } else {
+    const double g = exp_neg_half_square(u), gE = g * erfcx_nonneg(u * kRtHalf), lam = kRt2OverPi * g / (2.0 - gE);
+    val = log1p(-0.5 * gE); d1 = lam;
+    d2 = (lam == 0.0) ? 0.0 : -lam * (u + lam);      // (u = +inf: 0 (inf + 0) would be NaN)
+  }
+  return {val, d1, d2};
+}
+
+DNLP_OUTLINE DNLP_HD inline Rule3 normcdf_rules(double u) {
+  const double kRtHalf = 0.70710678118654752, kInvRt2Pi = 0.3989422804014327;
+  const double g = exp_neg_half_square(u), tail = 0.5 * g * erfcx_nonneg(fabs(u) * kRtHalf), phi = kInvRt2Pi * g;
+  return {(u <= 0.0) ? tail : 1.0 - tail, phi, (phi == 0.0) ? 0.0 : -u * phi};      // (u = +-inf: inf 0 would be NaN)
+}
+
+DNLP_OUTLINE DNLP_HD inline Rule3 loggamma_rules(double u) {
+  if (u > 0.0) { Rule3 r; r.val = lgamma(u); digamma_trigamma(u, r.d1, r.d2); return r; }
+  if (u == 0.0) return {kInf, -kInf, kInf};
+  const double nan = u - u + (kInf - kInf);          // below the domain, and NaN: NaN
+  return {nan, nan, nan};
 }
 
 // value, d/du, d2/du2 of a unary atom.  p_der is the derivative exponent (reference uses
@@ -78,6 +205,9 @@ DNLP_HD inline void unary_rules(int op, double u, double p_der, double p_fwd, do
       double q = 1.0 - u * u; val = atanh(u); d1 = 1.0 / q; d2 = 2.0 * u / (q * q); break; }
     case OP_XEXP: {                      // xexp.py:35-36,108-112,117-121
       double e = exp(u); val = u * e; d1 = e * (1.0 + u); d2 = e * (2.0 + u); break; }
+    case OP_LOG_NORMCDF: { const Rule3 r = log_normcdf_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
+    case OP_NORMCDF: { const Rule3 r = normcdf_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
+    case OP_LOGGAMMA: { const Rule3 r = loggamma_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
     default: val = d1 = d2 = 0.0;
   }
 }

@@ -117,6 +117,10 @@ ALIAS = {
     at.log_sum_exp: (PLAIN,),
     # no reference rule either (prod.py has no rule tags): the same alias, and no bounds -- a product has no domain
     at.Prod: (PLAIN,),
+    # no reference rule (the reference's log_normcdf.py / loggamma.py are DCP approximations without derivative rules, and it has
+    # no normcdf): the normal pair has no domain; loggamma's argument is always a new variable on [0, inf), like log's
+    at.log_normcdf: (PLAIN,), at.normcdf: (PLAIN,),
+    at.loggamma: (LOG_DOMAIN,),
 }
 
 

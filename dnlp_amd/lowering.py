@@ -43,6 +43,7 @@ from .expressions import Constant, Expression, Parameter, Variable
 # ---- opcodes (shared with csrc/tape.h) ---------------------------------------------------
 OP_EXP, OP_LOG, OP_ENTR, OP_LOGISTIC, OP_POWER = 1, 2, 3, 4, 5
 OP_SIN, OP_COS, OP_TAN, OP_SINH, OP_TANH, OP_ASINH, OP_ATANH, OP_XEXP = 6, 7, 8, 9, 10, 11, 12, 13
+OP_LOG_NORMCDF, OP_NORMCDF, OP_LOGGAMMA = 14, 15, 16     # exact statistical atoms (csrc/atom_math.h), beyond the reference's set
 OP_MUL, OP_REL_ENTR = 20, 21
 OP_QUAD_FORM_DENSE, OP_QUAD_FORM_SPARSE, OP_QUAD_OVER_LIN, OP_MATMUL = 30, 31, 32, 33
 OP_LOG_SUM_EXP = 34          # row class: many short (or few long) reductions, one dense Hessian block per row
@@ -53,6 +54,7 @@ UNARY_OPS = {
     at.exp: OP_EXP, at.log: OP_LOG, at.entr: OP_ENTR, at.logistic: OP_LOGISTIC,
     at.sin: OP_SIN, at.cos: OP_COS, at.tan: OP_TAN, at.sinh: OP_SINH, at.tanh: OP_TANH,
     at.asinh: OP_ASINH, at.atanh: OP_ATANH, at.xexp: OP_XEXP,
+    at.log_normcdf: OP_LOG_NORMCDF, at.normcdf: OP_NORMCDF, at.loggamma: OP_LOGGAMMA,
 }
 
 # dense quad_form blocks up to this order are also listed in the COO Hessian pattern
