@@ -1188,6 +1188,68 @@ def prod(expr, axis=None, keepdims=False):
     return Prod(Expression.cast_to_const(expr), axis, keepdims)
 
 
+class log_det(Atom):
+    """log det A of a square matrix (reference atoms/log_det.py: concave, neither increasing nor decreasing, domain A >> 0).
+    The reference gives the atom a gradient but no rule tags, no second derivative and no canonical form, so its
+    solve(nlp=True) rejects it; the function is smooth on its domain, so it is tagged ESR and HSR here like log, and it is a
+    tape op of its own (lowering.py OP_LOG_DET).  The sign is unknown: the reference's (True, False) is wrong wherever
+    det A < 1."""
+
+    def __init__(self, A):
+        super().__init__(A)
+
+    def validate_arguments(self):
+        X = self.args[0]
+        if not len(X.shape) == 2 or X.shape[0] != X.shape[1]:
+            raise TypeError("The argument to log_det must be a 2-d square array.")
+
+    def shape_from_args(self):
+        return ()
+
+    def numeric(self, values):
+        """slogdet of the symmetric part; -inf where that is not positive definite (reference log_det.py:36-48, which
+        looks at the sign of the determinant alone and so takes diag(-1, -1, 1) for a point of the domain)."""
+        A = _dense(values[0])
+        sym = (A + A.T) / 2
+        sign, logdet = np.linalg.slogdet(sym)
+        if not np.isclose(sign, 1) or not np.all(np.linalg.eigvalsh(sym) > 0):
+            return -np.inf
+        return logdet
+
+    def sign_from_args(self):
+        return (False, False)
+
+    def is_atom_convex(self):
+        return False
+
+    def is_atom_concave(self):
+        return True
+
+    def is_atom_esr(self):
+        return True
+
+    def is_atom_hsr(self):
+        return True
+
+    def is_incr(self, idx):
+        return False
+
+    def is_decr(self, idx):
+        return False
+
+    def point_in_domain(self):
+        return np.eye(self.args[0].shape[0])
+
+
+def trace(expr):
+    """Sum of the diagonal entries of a square matrix (reference atoms/affine/trace.py), through existing affine atoms:
+    the sum of the entrywise product with the identity."""
+    expr = Expression.cast_to_const(expr)
+    if expr.ndim != 2 or expr.shape[0] != expr.shape[1]:
+        raise ValueError("Argument to trace must be a square matrix.")
+    return sum(multiply(np.eye(expr.shape[0]), expr))
+
+
 class norm1(_AxisAtom):
     """Sum of absolute values (reference atoms/norm1.py): ESR only."""
 

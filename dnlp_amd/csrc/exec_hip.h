@@ -1378,9 +1378,10 @@ struct HipExec : HostControlled {
     };
     auto waves = [](const RowTable& t) { return (t.units + kBlock / 64 - 1) / (kBlock / 64); };
     auto spread = [&](const RowTable& t) { return with_h && t.units > 0 ? (t.hunits + kBlock - 1) / kBlock : 0; };
-    const RowTable &ls = tab[0], &ll = tab[1], &ps = tab[2], &pl = tab[3], &qs = tab[4], &ql = tab[5];
-    static_assert(kRowMembers == 3 && kRowForms == 2 && row_member(0).op == OP_LOG_SUM_EXP && row_member(1).op == OP_PROD &&
-                  row_member(2).op == OP_QUAD_OVER_LIN_ROWS, "the launches below follow the table of members");
+    const RowTable &ls = tab[0], &ll = tab[1], &ps = tab[2], &pl = tab[3], &qs = tab[4], &ql = tab[5], &ds = tab[6], &dl = tab[7];
+    static_assert(kRowMembers == 4 && kRowForms == 2 && row_member(0).op == OP_LOG_SUM_EXP && row_member(1).op == OP_PROD &&
+                  row_member(2).op == OP_QUAD_OVER_LIN_ROWS && row_member(3).op == OP_LOG_DET,
+                  "the launches below follow the table of members");
     go(sweep_rows_kernel, waves(ls), ls, gidx, x, z, dv, hv, w, h);
     go(sweep_rows_long_kernel, ll.units, ll, gidx, x, z, dv);
     go(sweep_rows_hess_kernel, spread(ll), ll, static_cast<const double*>(dv), hv, w);
@@ -1389,6 +1390,9 @@ struct HipExec : HostControlled {
     go(sweep_prod_hess_kernel, spread(pl), pl, static_cast<const double*>(dv), hv, w);
     go(sweep_qol_kernel, waves(qs), qs, gidx, x, z, dv, hv, w, h);
     go(sweep_qol_long_kernel, ql.units, ql, gidx, x, z, dv, hv, w, h);
+    go(sweep_logdet_kernel, waves(ds), ds, gidx, x, z, dv, hv, w, h);
+    go(sweep_logdet_long_kernel, dl.units, dl, gidx, x, z, dv);
+    go(sweep_logdet_hess_kernel, spread(dl), dl, static_cast<const double*>(dv), hv, w);
     if (launched) DNLP_LAUNCH_CHECK();
   }
   // Small systems: one workgroup walks all levels (one launch).  Large ones (>= 8192 pivot

@@ -1,8 +1,8 @@
 // Tape sweep over the row-class segments in the host-driven device space: the hand-written forms of the rules that
-// model.h states (sweep_lse_segment, sweep_prod_segment, sweep_qol_rows_segment).  Included by exec_hip.h.
+// model.h states (sweep_lse_segment, sweep_prod_segment, sweep_qol_rows_segment, sweep_logdet_segment).  Included by exec_hip.h.
 //
 // Every launch walks one RowTable (row_class.h: the segments of one member in one kernel form) by its prefix of work, so
-// a sweep is at most eight launches whatever the number of segments and rows, and a kernel serves one member (a table
+// a sweep is at most eleven launches whatever the number of segments and rows, and a kernel serves one member (a table
 // with an opcode column would make it three launches, at the price of one kernel text with the registers of the largest
 // member).  The order of every sum and product depends on (K, form) alone: a sweep repeats bit for bit.  No
 // floating-point atomics.
@@ -404,4 +404,115 @@ __global__ void __launch_bounds__(kBlock) sweep_qol_long_kernel(RowTable t, cons
     dv[t.doff[s] + MK + row] = -ss / (y * y);
     if (with_h) hv[t.hoff[s] + MK + row] = 2.0 * wr * ss / (y * y * y);
   }
+}
+
+// ---- log_det ----
+// A segment is one matrix A of order n (RowTable::ord), its K = n^2 entries in F order: entry l is (i, j) = (l % n, l / n).
+// The rule is Gauss-Jordan without pivoting (row_class.h logdet_row states it): n dependent steps, each needing the pivot,
+// the pivot row and the pivot column; afterwards the lanes hold B = inv(A) and d[i + j n] = B_ji.  No branch on the data:
+// `ok` (every pivot > 0) selects NaN at the stores, and the Hessian entries inherit it from d.
+//
+// Short form (n <= 8, K <= 64): one entry per lane; pivot, a_kj and a_ik come from the owning lanes by __shfl.  No LDS.
+// (M = 1, so a wavefront holds one matrix; the lanes beyond K run the same steps on zeros and store nothing.)
+__global__ void __launch_bounds__(kBlock) sweep_logdet_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                              double* __restrict__ z, double* __restrict__ dv,
+                                                              double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  ShortRow w;
+  if (!short_row(t, gidx, x, 0.0, w)) return;
+  const int n = static_cast<int>(t.ord[w.s]), lg = w.lg;
+  const int g0 = w.lane & ~(w.G - 1);                  // first lane of this lane's group
+  const int l = w.l < w.K ? w.l : 0;                   // (padding lanes follow entry 0: every fetch stays inside the group)
+  const int i = l % n, j = l / n;
+  double a = w.u, zs = 0.0;
+  bool ok = true;
+  for (int k = 0; k < n; ++k) {
+    const double piv = __shfl(a, g0 + k + k * n), rk = __shfl(a, g0 + k + j * n), f = __shfl(a, g0 + i + k * n);
+    ok = ok && (piv > 0.0);
+    zs += log(piv);
+    const double akj = j == k ? 1.0 / piv : rk / piv;  // the new a_kj, a_kk among them
+    a = i == k ? akj : (j == k ? -f * akj : a - f * akj);
+  }
+  const double nan = kInf - kInf;
+  const double g = ok ? __shfl(a, g0 + j + i * n) : nan;           // d[i + j n] = B_ji
+  if (w.valid) {
+    dv[t.doff[w.s] + w.e] = g;
+    if (w.l == 0) z[t.zoff[w.s] + w.r] = ok ? zs : nan;
+  }
+  if (!with_h) return;
+  short_row_triangles(t, w, w.K * (w.K + 1) / 2, false, hv, ww, [=](int row, int qa, int qb, bool) {
+    const int b0 = row << lg;
+    return -(__shfl(g, b0 + qb % n + (qa / n) * n) * __shfl(g, b0 + qa % n + (qb / n) * n));
+  });
+}
+
+// Long form (9 <= n <= 45, K <= kRowWaveMax = 2048): one wavefront per matrix, the matrix in REGISTERS, 32 entries per lane
+// (entry l = lane + 64 q), indexed by the unrolled q only (a run-time index would send the array to scratch).  Where the
+// lane's entries stand is taken once: per entry the LDS byte offsets of slot j of a row array and of slot i of a column
+// array, which are also what a step compares against (i == k, j == k); an entry beyond K gets slot n of both, which no
+// step names and which lies inside the n + 1 slots of each array.  Pivot row and pivot column of step k + 1 are posted to
+// the wavefront's own LDS arrays by their owners while step k updates them (two pairs of arrays, by the parity of k);
+// lanes 0 .. n - 1 divide the posted row by the pivot into a fifth array, and all lanes read that and the column back.
+// The four wavefronts of a workgroup share a segment, hence n: a wavefront without a matrix walks the same steps, so the
+// two barriers of a step are met by all.
+constexpr int kLogdetMaxN = 45;
+static_assert((kLogdetMaxN + 1) * (kLogdetMaxN + 1) > kRowWaveMax && kLogdetMaxN * kLogdetMaxN <= kRowWaveMax, "the largest order whose entries fit one wavefront's 32 per lane");
+constexpr int kLogdetPerLane = static_cast<int>(kRowWaveMax / 64);
+constexpr int kLogdetSlots = kLogdetMaxN + 1;
+__global__ void __launch_bounds__(kBlock) sweep_logdet_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                   double* __restrict__ z, double* __restrict__ dv) {
+  // per wavefront: (row, column) as posted for even steps, the same for odd steps, the row divided by its pivot
+  __shared__ double sm[(kBlock / 64) * 5 * kLogdetSlots];
+  const LongRow w = long_row(t, gidx, x);
+  const int n = static_cast<int>(t.ord[w.s]), Kon = static_cast<int>(w.Kon);
+  char* const base = reinterpret_cast<char*>(sm + w.wid * 5 * kLogdetSlots);
+  constexpr unsigned kCol = kLogdetSlots * 8, kPair = 2 * kLogdetSlots * 8, kNrm = 4 * kLogdetSlots * 8;      // byte offsets
+  auto at = [base](unsigned off) -> double& { return *reinterpret_cast<double*>(base + off); };
+  double a[kLogdetPerLane];
+  unsigned oj[kLogdetPerLane], oi[kLogdetPerLane];
+#pragma unroll
+  for (int q = 0; q < kLogdetPerLane; ++q) {
+    const int l = w.lane + 64 * q;
+    const bool on = l < Kon;
+    a[q] = on ? w.u(l) : 0.0;
+    oj[q] = 8u * static_cast<unsigned>(on ? l / n : n);
+    oi[q] = 8u * static_cast<unsigned>(on ? l % n : n);
+    if (oi[q] == 0u) at(oj[q]) = a[q];                 // row 0 and column 0 for step 0
+    if (oj[q] == 0u) at(kCol + oi[q]) = a[q];
+  }
+  bool ok = true;
+  double zs = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const unsigned k8 = 8u * static_cast<unsigned>(k), cur = (k & 1) ? kPair : 0u, nxt = kPair - cur;
+    __syncthreads();
+    const double piv = at(cur + k8);
+    ok = ok && (piv > 0.0);
+    zs += log(piv);
+    if (w.lane < n) at(kNrm + 8u * w.lane) = w.lane == k ? 1.0 / piv : at(cur + 8u * w.lane) / piv;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kLogdetPerLane; ++q) {
+      const double akj = at(kNrm + oj[q]), f = at(cur + kCol + oi[q]);
+      const double v = oi[q] == k8 ? akj : (oj[q] == k8 ? -f * akj : a[q] - f * akj);
+      a[q] = v;
+      if (oi[q] == k8 + 8u) at(nxt + oj[q]) = v;
+      if (oj[q] == k8 + 8u) at(nxt + kCol + oi[q]) = v;
+    }
+  }
+  const double nan = kInf - kInf;
+  double* __restrict__ dr = dv + t.doff[w.s] + w.base;
+#pragma unroll
+  for (int q = 0; q < kLogdetPerLane; ++q)                            // B_ij is the derivative by entry (j, i)
+    if (w.lane + 64 * q < Kon) dr[(oj[q] >> 3) + (oi[q] >> 3) * n] = ok ? a[q] : nan;
+  if (w.rowon && w.lane == 0) z[t.zoff[w.s] + w.row] = ok ? zs : nan;
+}
+
+// h[(a, b)] = -w d[k + j n] d[i + l n] for a = i + j n >= b = k + l n, out of the d slots the launch before filled
+__global__ void __launch_bounds__(kBlock) sweep_logdet_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
+                                                                   const double* __restrict__ ww) {
+  SpreadEntry en;
+  if (!spread_entry(t, false, en)) return;
+  const unsigned n = static_cast<unsigned>(t.ord[en.s]);
+  const double* __restrict__ dr = dv + t.doff[en.s] + static_cast<i64>(en.row) * en.K;
+  const double p = dr[en.j % n + (en.i / n) * n], q = dr[en.i % n + (en.j / n) * n];
+  hv[t.hoff[en.s] + en.qa] = ww[t.zoff[en.s] + en.row] * -(p * q);
 }

@@ -246,6 +246,7 @@ struct Model {
       if (g.op == OP_LOG_SUM_EXP) sweep_lse_segment(g, x, with_h);
       else if (g.op == OP_PROD) sweep_prod_segment(g, x, with_h);
       else if (g.op == OP_QUAD_OVER_LIN_ROWS) sweep_qol_rows_segment(g, x, with_h);
+      else if (g.op == OP_LOG_DET) sweep_logdet_segment(g, x, with_h);
       else DNLP_FAIL("row-class segment with an unknown opcode");
     }
   }
@@ -399,6 +400,37 @@ struct Model {
         hv[e] = 2.0 * wz / y;
         hv[M * K + M + e] = -2.0 * wz * u / (y * y);
       }
+    });
+  }
+
+  // OP_LOG_DET (lowering.py _lower_log_det; the reference's log_det.py has a gradient and no second derivative).  One row
+  // holds the K = n^2 entries of a matrix A of order n = d2 in F order.  The rule is row_class.h logdet_row -- Gauss-Jordan
+  // without pivoting, which for the symmetric argument of the canonical form succeeds exactly where A is positive
+  // definite -- and with B = inv(A):
+  //   z = sum_k log pivot_k        d[i + j n] = B_ji        h[(a, b)] = -w d[k + j n] d[i + l n],  a = i + j n >= b = k + l n
+  // (the packed lower triangle over the n^2 entries, row-major).  A pivot <= 0 or NaN: z, every d and, through d, every h
+  // of the row are NaN.  Two maps -- rows (copy into the d slots, eliminate there, transpose in place, write z), Hessian
+  // entries (products out of the d slots); nothing is parked.
+  DNLP_HD void sweep_logdet_segment(const SegHost& g, const double* x, bool with_h) {
+    DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
+    const i32* gidx = t.gidx;
+    const i64 M = g.d0, K = g.d1, n = g.d2, T = K * (K + 1) / 2, a0b = g.a0_base, a0o = g.a0_off;
+    double* z = xz + t.N + g.zoff;
+    double* dv = dvals + g.doff;
+    double* hv = hvals + g.hoff;
+    const double* ww = w + g.zoff;
+    ex->map(M, [=] DNLP_HD(i64 r) {
+      double* a = dv + r * K;
+      for (i64 l = 0; l < K; ++l) a[l] = x[arg_at(a0b, a0o, gidx, r * K + l)];
+      z[r] = logdet_row(a, n);
+    });
+    if (!with_h) return;
+    ex->map(M * T, [=] DNLP_HD(i64 e) {
+      const i64 r = e / T;
+      i64 a, b;
+      tri_decode(e - r * T, false, a, b);
+      const double* d = dv + r * K;
+      hv[e] = -ww[r] * d[b % n + (a / n) * n] * d[a % n + (b / n) * n];
     });
   }
 

@@ -15,22 +15,25 @@ namespace dnlp {
 // first derivative (by the denominator).  `parks`: the generic sweep keeps two numbers per row in an N-vector between
 // its maps (model.h), so load_rows refuses 2 M > N.  `two_args`: a second argument with one entry per row.
 // `spread_hess`: the Hessian entries of its long rows are written by a launch of their own that walks RowTable::hstart.
+// `square`: a segment is ONE row (M = 1) that holds the K = n^2 entries of a matrix of order n = d2 in F order, and the
+// whole row is one wavefront's work, so load_rows refuses K > kRowWaveMax.
 struct RowMember {
   int op;
   const char* name;          // in messages
   int tri;
-  bool parks, two_args, spread_hess;
+  bool parks, two_args, spread_hess, square;
   DNLP_HD constexpr i64 row_tri(i64 K) const { return tri == 0 ? 0 : (tri < 0 ? K * (K - 1) / 2 : K * (K + 1) / 2); }
   DNLP_HD constexpr i64 row_hcount(i64 K) const { return tri == 0 ? 2 * K + 1 : row_tri(K); }
   DNLP_HD constexpr i64 row_dcount(i64 K) const { return two_args ? K + 1 : K; }
 };
-constexpr int kRowMembers = 3;
+constexpr int kRowMembers = 4;
 // (the order of the table is the order of the device launches and of TapeView::row_tab)
 DNLP_HD constexpr RowMember row_member(int k) {
   constexpr RowMember members[kRowMembers] = {
-    {OP_LOG_SUM_EXP, "log_sum_exp", +1, true, false, true},
-    {OP_PROD, "prod", -1, true, false, true},
-    {OP_QUAD_OVER_LIN_ROWS, "quad_over_lin_rows", 0, false, true, false},
+    {OP_LOG_SUM_EXP, "log_sum_exp", +1, true, false, true, false},
+    {OP_PROD, "prod", -1, true, false, true, false},
+    {OP_QUAD_OVER_LIN_ROWS, "quad_over_lin_rows", 0, false, true, false, false},
+    {OP_LOG_DET, "log_det", +1, false, false, true, true},
   };
   return members[k];
 }
@@ -56,7 +59,8 @@ constexpr int kRowForms = 2;             // short (K <= kRowShortMax), long
 // launch work (wavefronts for the short form, workgroups for the long one), `hstart` the prefix of Hessian entries
 // (spread_hess members, long form).  `park` (prod, long form): what waits for the Hessian launch -- one double per row
 // slot 4 start[s] + row for the row's product, then, from 4 units on, a contiguous copy of every row's entries at
-// ustart[s] + row K (`ustart`: the prefix of M K).  `a1b` / `a1o`: the second argument of a two_args member.
+// ustart[s] + row K (`ustart`: the prefix of M K).  `a1b` / `a1o`: the second argument of a two_args member.  `ord` (a
+// `square` member): the order n of the segment's matrix -- a column of its own and not a root of K taken in the kernels.
 struct RowTable {
   i64 n = 0, units = 0, hunits = 0;
   i64 *start = nullptr, *hstart = nullptr;
@@ -64,6 +68,7 @@ struct RowTable {
   double* park = nullptr;
   i64* ustart = nullptr;
   i64 *a1b = nullptr, *a1o = nullptr;
+  i64* ord = nullptr;
 };
 
 // Index into x of entry e of an argument given as (base, offset): contiguous from `base`, or gathered through the tape's
@@ -87,6 +92,37 @@ DNLP_HD inline void tri_decode(int q, int& i, int& j) {
   while (i * (i + 1) / 2 > q) --i;
   while ((i + 1) * (i + 2) / 2 <= q) ++i;
   j = q - i * (i + 1) / 2;
+}
+
+// OP_LOG_DET, the rule of one matrix for the generic spaces (model.h sweep_logdet_segment): Gauss-Jordan WITHOUT pivoting,
+// in place on the n x n entries `a` (F order: entry (i, j) at i + j n), then the transposition in place.  On return `a`
+// holds the gradient inv(A)^T in the argument's own order and the result is sum_k log(pivot_k), summed in the order
+// k = 0 .. n - 1.  No branch on the data: the elimination runs to its end, and a pivot that is not positive (or NaN) makes
+// the result and every entry NaN at the end.  A function of its own on the device (the reason is atom_math.h DNLP_OUTLINE's).
+DNLP_OUTLINE DNLP_HD inline double logdet_row(double* a, i64 n) {
+  bool ok = true;
+  double z = 0.0;
+  for (i64 k = 0; k < n; ++k) {
+    const double piv = a[k + k * n];
+    ok = ok && (piv > 0.0);
+    z += log(piv);
+    a[k + k * n] = 1.0 / piv;
+    for (i64 j = 0; j < n; ++j) if (j != k) a[k + j * n] = a[k + j * n] / piv;
+    for (i64 i = 0; i < n; ++i) {
+      if (i == k) continue;
+      const double f = a[i + k * n];
+      a[i + k * n] = -f * a[k + k * n];
+      for (i64 j = 0; j < n; ++j) if (j != k) a[i + j * n] = a[i + j * n] - f * a[k + j * n];
+    }
+  }
+  const double nan = kInf - kInf;
+  for (i64 i = 0; i < n; ++i)
+    for (i64 j = 0; j <= i; ++j) {
+      const double lo = a[i + j * n], up = a[j + i * n];
+      a[i + j * n] = ok ? up : nan;
+      a[j + i * n] = ok ? lo : nan;
+    }
+  return ok ? z : nan;
 }
 
 }  // namespace dnlp

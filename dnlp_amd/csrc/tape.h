@@ -307,7 +307,7 @@ struct Tape : TapeView {
     std::vector<i64> fs{0}, a0b, a0o, a0l, a1b, a1o, a1l, zo, dof, ho, nn, e0, e1, e2;
     std::vector<i32> fop;
     std::vector<double> fp, fp2;
-    // OP_MATMUL (33) is elementwise-class (one unit per output entry) despite its opcode; op_is_row (34 .. 36) is the
+    // OP_MATMUL (33) is elementwise-class (one unit per output entry) despite its opcode; op_is_row (34 .. 37) is the
     // row class; 30 .. 32 are the reduction class; anything else is not a tape this library knows
     for (i64 s = 0; s < nseg; ++s) {
       const SegHost& g = h_segs[static_cast<size_t>(s)];
@@ -431,7 +431,7 @@ struct Tape : TapeView {
     for (int k = 0; k < kRowMembers; ++k)
     for (int lng = 0; lng < kRowForms; ++lng) {
       const RowMember mb = row_member(k);
-      std::vector<i64> st{0}, hs{0}, us{0}, K, M, a0b, a0o, a1b, a1o, zo, dof, ho;
+      std::vector<i64> st{0}, hs{0}, us{0}, K, M, a0b, a0o, a1b, a1o, zo, dof, ho, ord;
       for (i64 s : h_row_segs) {
         const SegHost& g = h_segs[static_cast<size_t>(s)];
         if (g.op != mb.op) continue;
@@ -443,6 +443,12 @@ struct Tape : TapeView {
         // rows that share entries across rows could outnumber the N-vector the generic sweep parks in.  The front-end
         // cannot produce such a tape (the argument is one variable).
         if (mb.parks && len > 1 && 2 * rows > N) throw std::runtime_error(name + " segment with more rows than half the variables: its rows share entries");
+        if (mb.square) {
+          // one matrix per segment, its order in d2; the whole matrix is one wavefront's registers on the device
+          if (g.d2 <= 0 || g.d2 * g.d2 != len) throw std::runtime_error(name + " segment whose row is not a square matrix: d2 * d2 != d1");
+          if (rows != 1) throw std::runtime_error(name + " segment with more than one matrix: M != 1");
+          if (len > kRowWaveMax) throw std::runtime_error(name + " segment with more than " + std::to_string(kRowWaveMax) + " entries: the order of a matrix ends at 45");
+        }
         if ((len <= kRowShortMax) == (lng != 0)) continue;
         i64 units;
         if (!lng) { i64 grp = 1; while (grp < len) grp <<= 1; const i64 per = 64 / grp; units = (rows + per - 1) / per; }   // wavefronts
@@ -452,7 +458,7 @@ struct Tape : TapeView {
         us.push_back(us.back() + g.dcount);
         K.push_back(len); M.push_back(rows); a0b.push_back(g.a0_base); a0o.push_back(g.a0_off);
         a1b.push_back(g.a1_base); a1o.push_back(g.a1_off);
-        zo.push_back(g.zoff); dof.push_back(g.doff); ho.push_back(g.hoff);
+        zo.push_back(g.zoff); dof.push_back(g.doff); ho.push_back(g.hoff); ord.push_back(g.d2);
       }
       RowTable& rt = h_row_tab[static_cast<size_t>(k * kRowForms + lng)];
       rt.n = static_cast<i64>(K.size());
@@ -464,6 +470,7 @@ struct Tape : TapeView {
       rt.a0b = up(a0b.data(), a0b.size()); rt.a0o = up(a0o.data(), a0o.size());
       rt.zoff = up(zo.data(), zo.size()); rt.doff = up(dof.data(), dof.size()); rt.hoff = up(ho.data(), ho.size());
       if (mb.two_args) { rt.a1b = up(a1b.data(), a1b.size()); rt.a1o = up(a1o.data(), a1o.size()); }
+      if (mb.square) rt.ord = up(ord.data(), ord.size());
       if (mb.op == OP_PROD && lng) {
         rt.ustart = up(us.data(), us.size());
         rt.park = ex->template alloc<double>(static_cast<size_t>(4 * rt.units + us.back()));

@@ -174,6 +174,27 @@ def _quad_over_lin_rows(atom, args):
     return _alias_arguments(atom, args, (PLAIN, Aux(nonneg=True, init=init_if_safely_positive)))
 
 
+def _log_det(atom, args):
+    """No reference rule (log_det.py has a gradient and nothing else).  Always a new variable T of the argument's shape with
+    the row T == (A + A.T) / 2 and no bounds -- a bare Variable is replaced too, like log's -- so the tape op reads n^2
+    distinct entries that are symmetric at every feasible point, where its unpivoted elimination succeeds exactly on the
+    positive definite cone (csrc/row_class.h logdet_row).  T starts at the symmetric part of A's value where its Cholesky
+    factorisation exists, otherwise at the identity."""
+    A = args[0]
+    n = A.shape[0]
+    T = Variable(A.shape)
+    start = np.eye(n)
+    if A.value is not None:
+        sym = (np.asarray(A.value, dtype=float) + np.asarray(A.value, dtype=float).T) / 2
+        try:
+            np.linalg.cholesky(sym)
+            start = sym
+        except np.linalg.LinAlgError:
+            pass
+    T.value = start
+    return atom.copy([T]), [T == (A + A.T) / 2]
+
+
 def _rel_entr(atom, args):
     """rel_entr_canon.py:29-61: x log(x / y)."""
     x, y = args
@@ -302,6 +323,7 @@ RULES.update({
     at.quad_over_lin: _quad_over_lin,
     at.QuadOverLinRows: _quad_over_lin_rows,
     at.rel_entr: _rel_entr,
+    at.log_det: _log_det,
     # rewrites
     at.kl_div: _kl_div,
     at.DivExpression: _quotient,

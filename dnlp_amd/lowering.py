@@ -48,6 +48,8 @@ OP_MUL, OP_REL_ENTR = 20, 21
 OP_QUAD_FORM_DENSE, OP_QUAD_FORM_SPARSE, OP_QUAD_OVER_LIN, OP_MATMUL = 30, 31, 32, 33
 OP_LOG_SUM_EXP = 34          # row class: many short (or few long) reductions, one dense Hessian block per row
 OP_PROD = 35                 # row class: the same rows with the STRICT lower triangle (a product's Hessian diagonal is zero)
+OP_LOG_DET = 37              # row class: one row holding the n^2 entries of a matrix of order n (dims[2]); the full triangle over them
+ROW_WAVE_MAX = 2048          # csrc/row_class.h kRowWaveMax: the entries one wavefront holds, 32 per lane
 OP_QUAD_OVER_LIN_ROWS = 36   # row class with a second argument (one denominator per row); an arrow of 2K + 1 Hessian entries per row
 
 UNARY_OPS = {
@@ -302,7 +304,7 @@ class Segment:
     hoff: int = 0
     hcount: int = 0
     aux: int = -1               # constant-matrix id (quad_form) / inner dimension (matmul)
-    dims: tuple = (0, 0, 0)     # matmul (m, k, p); row class (rows M, row length K, 0)
+    dims: tuple = (0, 0, 0)     # matmul (m, k, p); row class (rows M, row length K, 0 -- log_det: the matrix order n)
 
 
 @dataclass
@@ -763,11 +765,11 @@ class Lowerer:
             raise ValueError("%s of an empty argument." % name)
         return M, K, a0
 
-    def _row_class(self, e, name, op, diag):
-        """Row class (csrc/model.h sweep_rows): M rows of K entries (_row_geometry), one z per
-        row, d[r*K + l] = the row's derivative by entry l, h = the row's lower triangle in tril_indices order, with the
+    def _row_class(self, e, name, op, diag, geometry=None, dims2=0):
+        """Row class (csrc/model.h sweep_rows): M rows of K entries (_row_geometry, or the member's own `geometry`), one z
+        per row, d[r*K + l] = the row's derivative by entry l, h = the row's lower triangle in tril_indices order, with the
         diagonal (`diag` = 0) or without it (`diag` = -1)."""
-        M, K, a0 = self._row_geometry(e, name)
+        M, K, a0 = self._row_geometry(e, name) if geometry is None else geometry
         T = K * (K + 1) // 2 if diag == 0 else K * (K - 1) // 2
         if self.nh + M * T > 2 ** 31 - 1 or self.nd + M * K > 2 ** 31 - 1:
             raise ValueError("%s: %d row(s) of length %d need %d Hessian entries; the tape's 32-bit index "
@@ -778,7 +780,7 @@ class Lowerer:
             # the packed lower triangle would lose the factor 2 of a repeated index (as OP_MUL refuses a0 == a1)
             raise ValueError("%s: a row reads the same variable entry twice; its argument must have "
                              "distinct entries (run dnlp2smooth first)." % name)
-        seg = Segment(op=op, n=M, a0=a0, a1=None, zcount=M, dims=(M, K, 0))
+        seg = Segment(op=op, n=M, a0=a0, a1=None, zcount=M, dims=(M, K, dims2))
         z = self.Z + np.arange(M, dtype=np.int64)
         ii, jj = np.tril_indices(K, diag)
         self._new_segment(seg, np.repeat(z, K), a0, rows[:, ii].reshape(-1), rows[:, jj].reshape(-1), np.repeat(z, T))
@@ -792,6 +794,19 @@ class Lowerer:
         """d[r*K + l] = prod_{k != l} u_k; h: the STRICT lower triangle, (i, j) -> w_r prod_{k != i, j} u_k.  K = 1: no
         Hessian entry, d = 1, z = u."""
         return self._row_class(e, "prod", OP_PROD, -1)
+
+    def _lower_log_det(self, e):
+        """One matrix of order n is ONE row of K = n^2 entries: a0[i + j n] = x index of entry (i, j), the F order in which
+        a matrix variable lies in x; dims = (1, n^2, n).  d[i + j n] = inv(A)[j, i]; h: the lower triangle with its diagonal
+        over the n^2 entries, (a, b) -> -w d[k + j n] d[i + l n] for a = i + j n >= b = k + l n."""
+        a = e.args[0]
+        n = int(a.shape[0])
+        if n * n == 0:
+            raise ValueError("log_det of an empty argument.")
+        if n * n > ROW_WAVE_MAX:
+            raise ValueError("log_det: a matrix of order %d has %d entries; one wavefront holds the whole matrix, at most "
+                             "%d entries (order %d)." % (n, n * n, ROW_WAVE_MAX, int(np.sqrt(ROW_WAVE_MAX))))
+        return self._row_class(e, "log_det", OP_LOG_DET, 0, geometry=(1, n * n, self._gather(a)), dims2=n)
 
     def _lower_QuadOverLinRows(self, e):
         """Row class with two arguments: a0 as above, a1[r] = x index of row r's denominator.  d: M K entries dz_r/du_l at

@@ -1,9 +1,10 @@
 """Time per tape sweep of the row-class kernels (csrc/exec_hip_rows.h) of one atom, per shape, with and without the Hessian,
 against yardsticks measured in the same process, alternating sweep by sweep.
 
-    python tools/row_sweep_time.py --atom {log_sum_exp,prod,quad_over_lin_rows} [--tag NAME]      # on the MI355X
+    python tools/row_sweep_time.py --atom {log_sum_exp,prod,quad_over_lin_rows,log_det} [--tag NAME]      # on the MI355X
 
-Writes one line per shape to profiles/log_sum_exp_sweep.jsonl, prod_sweep.jsonl or quad_over_lin_rows_sweep.jsonl; with
+Writes one line per shape to profiles/log_sum_exp_sweep.jsonl, prod_sweep.jsonl, quad_over_lin_rows_sweep.jsonl or
+log_det_sweep.jsonl; with
 --tag NAME to profiles/<file>.<NAME>.jsonl instead, so that a run of another build of the library (DNLP_HIP_LIB) does not
 overwrite the current one.
 
@@ -17,7 +18,9 @@ shapes whose arrays fit the 256 MiB cache read from it).
 
 Yardsticks.  Every atom: the elementwise sweep (sweep_flat_kernel on a unary exp tape of the same algorithmic byte volume;
 8 read + 16 written, + 8 + 8 with the Hessian, per element).  prod also: the log_sum_exp kernels on a tape of the SAME
-(M, K).
+(M, K).  log_det (M matrices of order n, one segment each) also: the log_sum_exp kernels on M rows of K = n^2 entries --
+the same Hessian bytes and the same spread launch; its lines also give the time of one elimination step, the sweep without
+the Hessian over n.
 
 Algorithmic bytes of a row sweep.  log_sum_exp, prod: 8 + 4 read per entry (x and its index), 8 written per output, per d
 entry and, with the Hessian on, per h entry (+ 8 read per row for its weight); K (K + 1) / 2 Hessian entries per row,
@@ -49,18 +52,21 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 # (rows, row length).  Sizes whose numpy lowering stays within seconds: the Hessian pattern of 2e4 x 64 is 4e7 entries and
 # that of 16 x 4097 is 1.3e8; rows per shape are cut where they exceed ~3.4e7 entries.
 TRI_SHAPES = [(100000, 4), (100000, 10), (100000, 16), (5000, 64), (5000, 65), (500, 257), (2, 4097), (1, 8193)]
+LOGDET_SHAPES = [(1024, 3), (256, 8), (64, 16), (16, 32), (4, 45)]      # (matrices, order)
 QOL_SHAPES = [(100000, 2), (100000, 3), (100000, 10), (100000, 16), (5000, 64), (5000, 65), (500, 257), (2, 4097)]
 WARM, REPS, BLOCKS = 20, 200, 4
 TRACE_LIMIT_S = 400                              # per rocprofv3 child
 KERNELS = {"lse": ("sweep_rows_kernel", "sweep_rows_long_kernel", "sweep_rows_hess_kernel"),
            "prod": ("sweep_prod_kernel", "sweep_prod_long_kernel", "sweep_prod_hess_kernel"),
            "qol": ("sweep_qol_kernel", "sweep_qol_long_kernel"),
+           "logdet": ("sweep_logdet_kernel", "sweep_logdet_long_kernel", "sweep_logdet_hess_kernel"),
            "flat": ("sweep_flat_kernel",)}
 # per atom: its output file, its shapes, and the tapes of one sweep round in the order they are evaluated (the first is
 # the atom's own, the last the exp tape sized by the first one's bytes)
 ATOMS = {"log_sum_exp": ("log_sum_exp_sweep.jsonl", TRI_SHAPES, ("lse", "flat")),
          "prod": ("prod_sweep.jsonl", TRI_SHAPES, ("prod", "lse", "flat")),
-         "quad_over_lin_rows": ("quad_over_lin_rows_sweep.jsonl", QOL_SHAPES, ("qol", "flat"))}
+         "quad_over_lin_rows": ("quad_over_lin_rows_sweep.jsonl", QOL_SHAPES, ("qol", "flat")),
+         "log_det": ("log_det_sweep.jsonl", LOGDET_SHAPES, ("logdet", "lse", "flat"))}
 LOOP_M, LOOP_K = (100, 200, 400, 1000), 3      # (the ends are the two sizes to record; the others locate a crossing)
 LAUNCH_SEGMENTS = [(300, 3), (40, 2), (7, 16), (1000, 3), (5, 64), (64, 7), (9, 65), (3, 300), (2, 2049), (1, 4097), (11, 129), (90, 5)]
 LAUNCH_SWEEPS = 10
@@ -80,7 +86,7 @@ def exp_elements(nbytes, with_h):
 
 
 def launches(stream, K, with_h):
-    return 2 if stream in ("lse", "prod") and K > 64 and with_h else 1
+    return 2 if stream in ("lse", "prod", "logdet") and K > 64 and with_h else 1
 
 
 def form(K):
@@ -118,6 +124,12 @@ def _row_tapes(atom, M, K):
     import lse_problems as lp
     import prod_problems as pp
     import qol_rows_problems as qp
+    if atom == "log_det":                                   # (M matrices of order K: the row length is K * K)
+        import logdet_problems as lq
+        import logdet_reference as lr
+        mats = [lr.matrix(K, 100.0, False, seed=7000 + k) for k in range(M)]
+        tapes = [lq.matrices_tape(mats), lp.rows_tape([np.random.default_rng(K).standard_normal((M, K * K))], axis=1)]
+        return [(_device(t[0]),) + tuple(t[1:]) for t in tapes], (lambda with_h: tri_bytes(M, K * K, with_h, False)), 0
     axis = 1 if M > 1 else None
     rng = np.random.default_rng(K)
     if atom == "log_sum_exp":
@@ -188,9 +200,10 @@ def sweep_times(atom):
             got = times[(M, K, with_h)] = {s: [] for s in streams}
             for rep in range(WARM + REPS):
                 for s in streams:
-                    part = rows[pos:pos + launches(s, K, with_h)]
+                    L = K * K if atom == "log_det" else K
+                    part = rows[pos:pos + launches(s, L, with_h)]
                     pos += len(part)
-                    if len(part) != launches(s, K, with_h) or any(p[1] not in KERNELS[s] for p in part):
+                    if len(part) != launches(s, L, with_h) or any(p[1] not in KERNELS[s] for p in part):
                         raise SystemExit("unexpected kernel order at %d x %d: %r where %s was due" % (M, K, [p[1] for p in part], s))
                     if rep >= WARM:
                         got[s].append(sum(p[2] for p in part))
@@ -207,6 +220,8 @@ def shape_lines(atom):
             rec = {"M": M, "K": K, "form": form(K), "switch_group_to_wavefront": 64, "switch_wavefront_to_workgroup": 2048, "warm": WARM, "reps": REPS}
         elif atom == "prod":
             rec = {"M": M, "K": K, "form": form(K), "warm": WARM, "reps": REPS, "blocks": BLOCKS}
+        elif atom == "log_det":
+            rec = {"matrices": M, "n": K, "K": K * K, "form": form(K * K), "warm": WARM, "reps": REPS, "blocks": BLOCKS}
         else:
             rec = {"part": "a", "M": M, "K": K, "form": form(K), "gathered": bool(notes[(M, K)]), "warm": WARM, "reps": REPS, "blocks": BLOCKS}
         for with_h in (False, True):
@@ -228,6 +243,15 @@ def shape_lines(atom):
                             "lse_us_" + tag: 1e6 * tl, "lse_TBps_" + tag: lbytes / tl * 1e-12, "lse_spread_" + tag: spread(t["lse"]),
                             "flat_us_" + tag: 1e6 * tf, "flat_TBps_" + tag: ebytes / tf * 1e-12,
                             "time_over_lse_" + tag: tp / tl, "byte_rate_over_flat_" + tag: (nbytes / tp) / (ebytes / tf)})
+            elif atom == "log_det":
+                nbytes, td, tl = tri_bytes(M, K * K, with_h, False), mean["logdet"], mean["lse"]
+                ebytes = exp_elements(nbytes, with_h) * (40 if with_h else 24)
+                rec.update({"bytes_" + tag: nbytes, "logdet_us_" + tag: 1e6 * td, "logdet_us_min_" + tag: 1e-3 * float(np.min(t["logdet"])),
+                            "logdet_TBps_" + tag: nbytes / td * 1e-12,
+                            "lse_us_" + tag: 1e6 * tl, "lse_spread_" + tag: spread(t["lse"]),
+                            "flat_us_" + tag: 1e6 * tf, "time_over_lse_" + tag: td / tl})
+                if not with_h:
+                    rec["us_per_elimination_step"] = 1e6 * td / K
             else:
                 nbytes, tq = qol_bytes(M, K, with_h, bool(notes[(M, K)])), mean["qol"]
                 ebytes = exp_elements(nbytes, with_h) * (40 if with_h else 24)
