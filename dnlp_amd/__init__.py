@@ -16,13 +16,13 @@ from .settings import (  # noqa: F401
 from .error import DeviceUnavailableError, DNLPError, SolverError  # noqa: F401
 from .expressions import Constant, DeviceMatrix, Expression, Parameter, Variable  # noqa: F401
 from .atoms import (  # noqa: F401
-    AddExpression, DivExpression, MulExpression, NegExpression, Pnorm, Prod, Promote, QuadForm, QuadOverLinRows, Sum,
+    AddExpression, DivExpression, MatrixFrac, MulExpression, NegExpression, Pnorm, Prod, Promote, QuadForm, QuadOverLinRows, Sum,
     abs, asinh, atanh, broadcast_to, cos, entr, exp, geo_mean, hstack, huber, index, kl_div,
-    log, log_det, log_normcdf, log_sum_exp, loggamma, logistic, matmul, max, maximum, min, minimum, multiply, norm, norm1, norm2, norm_inf,
+    log, log_det, log_normcdf, log_sum_exp, loggamma, logistic, matmul, matrix_frac, max, maximum, min, minimum, multiply, norm, norm1, norm2, norm_inf,
     normcdf,
     pnorm, power, prod, promote, quad_form, quad_over_lin, quad_over_lin_rows, rel_entr, reshape, sin, sinh,
     special_index, sqrt, square, sum, sum_largest, sum_smallest, sum_squares, tan, tanh,
-    trace, transpose, vec, vstack, xexp,
+    tr_inv, trace, transpose, vec, vstack, xexp,
 )
 from .constraints import Equality, Inequality, NonNeg, NonPos, Zero  # noqa: F401
 from .problem import Maximize, Minimize, Problem  # noqa: F401

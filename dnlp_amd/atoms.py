@@ -15,6 +15,7 @@ from fractions import Fraction
 from typing import List, Tuple
 
 import numpy as np
+import scipy.linalg as sla
 import scipy.sparse as sp
 import scipy.special as special
 
@@ -1248,6 +1249,84 @@ def trace(expr):
     if expr.ndim != 2 or expr.shape[0] != expr.shape[1]:
         raise ValueError("Argument to trace must be a square matrix.")
     return sum(multiply(np.eye(expr.shape[0]), expr))
+
+
+class MatrixFrac(Atom):
+    """tr(X^T P^-1 X) with P a square matrix of order n and X an n x m matrix, a 1-D X of length n standing for n x 1
+    (reference atoms/matrix_frac.py: convex, nonnegative, neither increasing nor decreasing, domain P >> 0).  The reference
+    gives the atom a gradient but no rule tags, no second derivative and no canonical form; the function is smooth on its
+    domain, so it is tagged ESR and HSR here like log_det, and it is a tape op of its own (lowering.py OP_MATRIX_FRAC).
+    Built by `matrix_frac`, which rewrites a constant P to a sum of squares."""
+
+    def __init__(self, X, P):
+        super().__init__(X, P)
+
+    def validate_arguments(self):
+        X, P = self.args
+        if P.ndim != 2 or P.shape[0] != P.shape[1]:
+            raise ValueError("The second argument to matrix_frac must be a square matrix.")
+        if X.ndim == 0 or X.shape[0] != P.shape[0]:
+            raise ValueError("The arguments to matrix_frac have incompatible dimensions.")
+
+    def shape_from_args(self):
+        return ()
+
+    def numeric(self, values):
+        """tr(X^T inv(sym P) X) with sym P the symmetric part; inf where that is not positive definite (the reference's
+        matrix_frac.py:36-46 inverts whatever it is given)."""
+        X, P = _dense(values[0]), _dense(values[1])
+        X = X.reshape(P.shape[0], -1, order="F")
+        sym = (P + P.T) / 2
+        try:
+            L = np.linalg.cholesky(sym)
+        except np.linalg.LinAlgError:
+            return np.inf
+        return float(np.square(sla.solve_triangular(L, X, lower=True)).sum())
+
+    def sign_from_args(self):
+        return (True, False)
+
+    def is_atom_convex(self):
+        return True
+
+    def is_atom_concave(self):
+        return False
+
+    def is_atom_esr(self):
+        return True
+
+    def is_atom_hsr(self):
+        return True
+
+    def is_incr(self, idx):
+        return False
+
+    def is_decr(self, idx):
+        return False
+
+
+def matrix_frac(X, P):
+    """tr(X^T P^-1 X).  A constant P without parameters (an array among them) needs no op of its own, as in the
+    reference's wrapper (matrix_frac.py:147-153): with L the Cholesky factor of P's symmetric part the value is
+    sum_squares(inv(L) X).  Anything else is the atom MatrixFrac."""
+    X, P = Expression.cast_to_const(X), Expression.cast_to_const(P)
+    if not (P.is_constant() and not P.parameters()):
+        return MatrixFrac(X, P)
+    MatrixFrac(Constant(np.zeros(X.shape)), Constant(np.zeros(P.shape)))       # (the atom's own validation messages)
+    Pv = _dense(P.value)
+    try:
+        L = np.linalg.cholesky((Pv + Pv.T) / 2)
+    except np.linalg.LinAlgError:
+        raise ValueError("matrix_frac: the symmetric part of the constant second argument is not positive definite.")
+    return sum_squares(Constant(sla.solve_triangular(L, np.eye(L.shape[0]), lower=True)) @ X)
+
+
+def tr_inv(P):
+    """tr(P^-1) (reference atoms/tr_inv.py) = matrix_frac(I, P): no atom class of its own."""
+    P = Expression.cast_to_const(P)
+    if P.ndim != 2 or P.shape[0] != P.shape[1]:
+        raise ValueError("The argument %s to tr_inv must be a 2-d square array." % P.name())
+    return matrix_frac(np.eye(P.shape[0]), P)
 
 
 class norm1(_AxisAtom):

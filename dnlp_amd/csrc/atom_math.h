@@ -16,12 +16,13 @@ enum Op : int {
   OP_LOG_SUM_EXP = 34,     // row class (model.h sweep_rows): M rows of K entries, one dense K x K Hessian block per row
   OP_PROD = 35,            // row class: the same rows; the block's diagonal is zero and only the strict triangle is stored
   OP_QUAD_OVER_LIN_ROWS = 36,  // row class with a second argument: a denominator per row, an arrow of 2K + 1 Hessian entries
-  OP_LOG_DET = 37          // row class: ONE row holding the n x n entries of a matrix (d2 = n); the full triangle over those n^2 entries
+  OP_LOG_DET = 37,         // row class: ONE row holding the n x n entries of a matrix (d2 = n); the full triangle over those n^2 entries
+  OP_MATRIX_FRAC = 38      // row class: ONE row holding P (n x n, d2 = n) and then X (n x m); the full triangle over those n (n + m) entries
 };
 
 DNLP_HD inline bool op_is_flat(int op) { return op < OP_QUAD_FORM_DENSE; }
 // (constexpr: row_class.h checks its table of members against this at compile time)
-DNLP_HD constexpr inline bool op_is_row(int op) { return op >= OP_LOG_SUM_EXP && op <= OP_LOG_DET; }
+DNLP_HD constexpr inline bool op_is_row(int op) { return op >= OP_LOG_SUM_EXP && op <= OP_MATRIX_FRAC; }
 
 // integer-exponent fast paths keep x^2 etc. exact and cheap (pow() is ~50 instructions)
 DNLP_HD inline double pow_fast(double u, double p) {

@@ -844,7 +844,7 @@ __global__ void __launch_bounds__(kBlock) sweep_flat_kernel(FlatTable t, const d
   }
 }
 
-#include "exec_hip_rows.h"     // the row-class segments: sweep_rows_* / sweep_prod_* / sweep_qol_* kernels
+#include "exec_hip_rows.h"     // the row-class segments: sweep_rows_* / sweep_prod_* / sweep_qol_* / sweep_logdet_* / sweep_mfrac_* kernels
 
 // part[q * 1024 + block] = this block's share of sum_i V[q*N + i] * w[i] for q < k (k <= 32): all k dot products in one
 // sweep of w; vt_dot_finish_kernel adds the blocks' shares in block order (round 4: an atomic add per block landed in
@@ -1378,9 +1378,9 @@ struct HipExec : HostControlled {
     };
     auto waves = [](const RowTable& t) { return (t.units + kBlock / 64 - 1) / (kBlock / 64); };
     auto spread = [&](const RowTable& t) { return with_h && t.units > 0 ? (t.hunits + kBlock - 1) / kBlock : 0; };
-    const RowTable &ls = tab[0], &ll = tab[1], &ps = tab[2], &pl = tab[3], &qs = tab[4], &ql = tab[5], &ds = tab[6], &dl = tab[7];
-    static_assert(kRowMembers == 4 && kRowForms == 2 && row_member(0).op == OP_LOG_SUM_EXP && row_member(1).op == OP_PROD &&
-                  row_member(2).op == OP_QUAD_OVER_LIN_ROWS && row_member(3).op == OP_LOG_DET,
+    const RowTable &ls = tab[0], &ll = tab[1], &ps = tab[2], &pl = tab[3], &qs = tab[4], &ql = tab[5], &ds = tab[6], &dl = tab[7], &ms = tab[8], &ml = tab[9];
+    static_assert(kRowMembers == 5 && kRowForms == 2 && row_member(0).op == OP_LOG_SUM_EXP && row_member(1).op == OP_PROD &&
+                  row_member(2).op == OP_QUAD_OVER_LIN_ROWS && row_member(3).op == OP_LOG_DET && row_member(4).op == OP_MATRIX_FRAC,
                   "the launches below follow the table of members");
     go(sweep_rows_kernel, waves(ls), ls, gidx, x, z, dv, hv, w, h);
     go(sweep_rows_long_kernel, ll.units, ll, gidx, x, z, dv);
@@ -1393,6 +1393,9 @@ struct HipExec : HostControlled {
     go(sweep_logdet_kernel, waves(ds), ds, gidx, x, z, dv, hv, w, h);
     go(sweep_logdet_long_kernel, dl.units, dl, gidx, x, z, dv);
     go(sweep_logdet_hess_kernel, spread(dl), dl, static_cast<const double*>(dv), hv, w);
+    go(sweep_mfrac_kernel, waves(ms), ms, gidx, x, z, dv, hv, w, h);
+    go(sweep_mfrac_long_kernel, ml.units, ml, gidx, x, z, dv);
+    go(sweep_mfrac_hess_kernel, spread(ml), ml, static_cast<const double*>(dv), hv, w);
     if (launched) DNLP_LAUNCH_CHECK();
   }
   // Small systems: one workgroup walks all levels (one launch).  Large ones (>= 8192 pivot

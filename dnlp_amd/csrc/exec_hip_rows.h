@@ -1,8 +1,9 @@
 // Tape sweep over the row-class segments in the host-driven device space: the hand-written forms of the rules that
-// model.h states (sweep_lse_segment, sweep_prod_segment, sweep_qol_rows_segment, sweep_logdet_segment).  Included by exec_hip.h.
+// model.h states (sweep_lse_segment, sweep_prod_segment, sweep_qol_rows_segment, sweep_logdet_segment,
+// sweep_mfrac_segment).  Included by exec_hip.h.
 //
 // Every launch walks one RowTable (row_class.h: the segments of one member in one kernel form) by its prefix of work, so
-// a sweep is at most eleven launches whatever the number of segments and rows, and a kernel serves one member (a table
+// a sweep is at most fourteen launches whatever the number of segments and rows, and a kernel serves one member (a table
 // with an opcode column would make it three launches, at the price of one kernel text with the registers of the largest
 // member).  The order of every sum and product depends on (K, form) alone: a sweep repeats bit for bit.  No
 // floating-point atomics.
@@ -515,4 +516,142 @@ __global__ void __launch_bounds__(kBlock) sweep_logdet_hess_kernel(RowTable t, c
   const double* __restrict__ dr = dv + t.doff[en.s] + static_cast<i64>(en.row) * en.K;
   const double p = dr[en.j % n + (en.i / n) * n], q = dr[en.i % n + (en.j / n) * n];
   hv[t.hoff[en.s] + en.qa] = ww[t.zoff[en.s] + en.row] * -(p * q);
+}
+
+// ---- matrix_frac ----
+// A segment is P of order n (RowTable::ord) and X of n x m, its K = n (n + m) entries in the order P (F), X (F).  The rule
+// (row_class.h mfrac_row states it) is the first n steps of log_det's elimination on the bordered matrix [[P, X], [X^T, 0]]
+// of order N = K / n: afterwards it holds B = inv(P), W = B X, -V^T and -X^T B X, and a pivot that was not positive has
+// made every entry NaN, which every output inherits.  The kernel form follows N^2 (RowMember::work), not K.
+//
+// Short form (N <= 8): one entry of the BORDERED matrix per lane, l = i + j N; every lane fetches its own entry of the
+// argument (the mirror image X^T from the same x index as X, the zero block 0).  Pivot, row and column by __shfl as for
+// log_det; z, the m diagonal entries of the last block, summed in the order c = 0 .. m - 1 in every lane; lane e < K then
+// takes d[e] (m products for an entry of P).  No LDS.  One segment per wavefront (M = 1), as for log_det.
+__device__ __forceinline__ int mfrac_arg_of(int i, int j, int n) {       // the argument entry behind bordered (i, j); -1: the zero block
+  return (i < n && j < n) ? i + j * n : (i < n ? n * n + i + (j - n) * n : (j < n ? n * n + j + (i - n) * n : -1));
+}
+__global__ void __launch_bounds__(kBlock) sweep_mfrac_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                             double* __restrict__ z, double* __restrict__ dv,
+                                                             double* __restrict__ hv, const double* __restrict__ ww, int with_h) {
+  const int lane = threadIdx.x & 63;
+  const i64 wv = static_cast<i64>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  if (wv >= t.units) return;
+  const i64 s = row_find(t.start, t.n, wv);
+  const int K = static_cast<int>(t.K[s]), n = static_cast<int>(t.ord[s]), N = K / n, NN = N * N;
+  const int lb = lane < NN ? lane : 0;                  // (lanes beyond the matrix follow entry 0 and store nothing)
+  const int i = lb % N, j = lb / N;
+  const int arg = mfrac_arg_of(i, j, n);
+  const i64 a0b = t.a0b[s];
+  double a = arg >= 0 ? x[a0b >= 0 ? a0b + arg : gidx[t.a0o[s] + arg]] : 0.0;
+  bool ok = true;
+  for (int k = 0; k < n; ++k) {
+    const double piv = __shfl(a, k + k * N), rk = __shfl(a, k + j * N), f = __shfl(a, i + k * N);
+    ok = ok && (piv > 0.0);
+    const double akj = j == k ? 1.0 / piv : rk / piv;
+    a = i == k ? akj : (j == k ? -f * akj : a - f * akj);
+  }
+  const double nan = kInf - kInf;
+  a = ok ? a : nan;
+  double zs = 0.0;
+  for (int c = n; c < N; ++c) zs += __shfl(a, c + c * N);
+  // d of argument entry e = lane (lanes beyond K follow entry 0)
+  const int e = lane < K ? lane : 0;
+  const bool inP = e < n * n;
+  const int ei = inP ? e % n : (e - n * n) % n, ej = inP ? e / n : n + (e - n * n) / n;
+  const double wic = __shfl(a, ei + ej * N), vic = __shfl(a, ej + ei * N);
+  double gs = 0.0;
+  for (int c = n; c < N; ++c) gs += __shfl(a, c + ei * N) * __shfl(a, ej + c * N);
+  const double g = inP ? gs : wic - vic;
+  if (lane < K) dv[t.doff[s] + lane] = g;
+  if (lane == 0) z[t.zoff[s]] = -zs;
+  if (!with_h) return;
+  ShortRow w{s, 1, 0, 0, lane, K, 64, 6, 1, lane, lane, lane < K, 0.0};
+  const int nn = n * n;
+  short_row_triangles(t, w, K * (K + 1) / 2, false, hv, ww, [=](int, int p, int q, bool) {
+    // (every lane makes every fetch: the three kinds differ in their indices only)
+    const bool pP = p < nn, qP = q < nn;
+    const int pi = pP ? p % n : (p - nn) % n, pj = pP ? p / n : n + (p - nn) / n;
+    const int qi = qP ? q % n : (q - nn) % n, qj = qP ? q / n : n + (q - nn) / n;
+    // PP: B_li d[k + j n], B_jk d[i + l n] with (i, j) = p, (k, l) = q.  XP: B_ki W_jc, L_ci B_jk with (k, c) = p, (i, j) = q.
+    // XX: B_ij, B_ji with (i, c) = p, (j, d) = q.
+    const double u1 = __shfl(a, pP ? qj + pi * N : pi + qi * N);
+    const double u2 = __shfl(a, pP ? pj + qi * N : (qP ? qj + pi * N : qi + pi * N));
+    const double g1 = __shfl(g, pP ? qi + pj * n : 0), g2 = __shfl(g, pP ? pi + qj * n : 0);
+    const double a1 = __shfl(a, !pP && qP ? qj + pj * N : 0), a2 = __shfl(a, !pP && qP ? pj + qi * N : 0);
+    const double v1 = pP ? g1 : a1, v2 = pP ? g2 : a2;
+    const double sx = u1 + u2;
+    return pP ? -(u1 * v1 + u2 * v2) : (qP ? -(u1 * v1 - v2 * u2) : (pj == qj ? sx : (sx == sx ? 0.0 : sx)));
+  });
+}
+
+// Long form (9 <= N <= 45): log_det's, on the bordered matrix and over n steps.  The wavefront then parks the swept matrix
+// (RowTable::park, N^2 doubles from ustart[s]; NaN throughout after a pivot that was not positive), writes z through the
+// fixed DPP tree, and -- after a barrier, out of what it has just parked -- the K first derivatives, entry e = lane + 64 q.
+__global__ void __launch_bounds__(kBlock) sweep_mfrac_long_kernel(RowTable t, const i32* __restrict__ gidx, const double* __restrict__ x,
+                                                                  double* __restrict__ z, double* __restrict__ dv) {
+  __shared__ double sm[(kBlock / 64) * 5 * kLogdetSlots];
+  const LongRow w = long_row(t, gidx, x);
+  const int n = static_cast<int>(t.ord[w.s]), K = static_cast<int>(w.K), N = K / n, NNon = w.rowon ? N * N : 0;
+  char* const base = reinterpret_cast<char*>(sm + w.wid * 5 * kLogdetSlots);
+  constexpr unsigned kCol = kLogdetSlots * 8, kPair = 2 * kLogdetSlots * 8, kNrm = 4 * kLogdetSlots * 8;      // byte offsets
+  auto at = [base](unsigned off) -> double& { return *reinterpret_cast<double*>(base + off); };
+  double a[kLogdetPerLane];
+  unsigned oj[kLogdetPerLane], oi[kLogdetPerLane];
+#pragma unroll
+  for (int q = 0; q < kLogdetPerLane; ++q) {
+    const int l = w.lane + 64 * q;
+    const bool on = l < NNon;
+    const int i = on ? l % N : N, j = on ? l / N : N;
+    const int arg = on ? mfrac_arg_of(i, j, n) : -1;
+    a[q] = arg >= 0 ? w.u(arg) : 0.0;
+    oj[q] = 8u * static_cast<unsigned>(j);
+    oi[q] = 8u * static_cast<unsigned>(i);
+    if (oi[q] == 0u) at(oj[q]) = a[q];                 // row 0 and column 0 for step 0
+    if (oj[q] == 0u) at(kCol + oi[q]) = a[q];
+  }
+  bool ok = true;
+  double zs = 0.0;
+  for (int k = 0; k < n; ++k) {                        // (log_det's step on order N; lanes 0 .. N - 1 divide the row)
+    const unsigned k8 = 8u * static_cast<unsigned>(k), cur = (k & 1) ? kPair : 0u, nxt = kPair - cur;
+    __syncthreads();
+    const double piv = at(cur + k8);
+    ok = ok && (piv > 0.0);
+    if (w.lane < N) at(kNrm + 8u * w.lane) = w.lane == k ? 1.0 / piv : at(cur + 8u * w.lane) / piv;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kLogdetPerLane; ++q) {
+      const double akj = at(kNrm + oj[q]), f = at(cur + kCol + oi[q]);
+      const double v = oi[q] == k8 ? akj : (oj[q] == k8 ? -f * akj : a[q] - f * akj);
+      a[q] = v;
+      if (oi[q] == k8 + 8u) at(nxt + oj[q]) = v;
+      if (oj[q] == k8 + 8u) at(nxt + kCol + oi[q]) = v;
+    }
+  }
+  const double nan = kInf - kInf;
+  const unsigned n8 = 8u * static_cast<unsigned>(n);
+  double* __restrict__ pk = t.park + t.ustart[w.s];
+#pragma unroll
+  for (int q = 0; q < kLogdetPerLane; ++q) {
+    a[q] = ok ? a[q] : nan;
+    if (w.lane + 64 * q < NNon) pk[w.lane + 64 * q] = a[q];
+    if (oi[q] == oj[q] && oi[q] >= n8 && w.lane + 64 * q < NNon) zs += a[q];
+  }
+  zs = wave_all_sum(zs);
+  if (w.rowon && w.lane == 0) z[t.zoff[w.s]] = -zs;
+  __threadfence_block();
+  __syncthreads();
+  if (!w.rowon) return;
+  double* __restrict__ dr = dv + t.doff[w.s];
+  for (int e = w.lane; e < K; e += 64) dr[e] = mfrac_d(pk, N, n, e);
+}
+
+// Spread Hessian launch: entry (p, q) of the segment's packed triangle out of the parked matrix and the d slots
+// (row_class.h mfrac_h classifies it by comparison with n^2)
+__global__ void __launch_bounds__(kBlock) sweep_mfrac_hess_kernel(RowTable t, const double* __restrict__ dv, double* __restrict__ hv,
+                                                                  const double* __restrict__ ww) {
+  SpreadEntry en;
+  if (!spread_entry(t, false, en)) return;
+  const i64 n = t.ord[en.s], N = static_cast<i64>(en.K) / n;
+  hv[t.hoff[en.s] + en.qa] = ww[t.zoff[en.s]] * mfrac_h(t.park + t.ustart[en.s], dv + t.doff[en.s], N, n, en.i, en.j);
 }

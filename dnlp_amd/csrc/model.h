@@ -32,7 +32,7 @@ struct Model {
   VecP<E> w;                // Z
   VecP<E> sl;               // [sigma; lambda]
   VecP<E> Hs;               // nnzH sparse-part Hessian values
-  VecP<E> tmpN;             // N scratch (dense quad_form products)
+  VecP<E> tmpN;             // N scratch (dense quad_form products), then TapeView::row_work() more (sweep_mfrac_segment)
   double* dense_w = nullptr;   // control space: current weight 2*w_z of every dense block
 
   DNLP_HD i64 N() const { return t.N; }
@@ -54,7 +54,7 @@ struct Model {
     w = ex->template alloc<double>(static_cast<size_t>(t.Z));
     sl = ex->template alloc<double>(static_cast<size_t>(1 + t.m));
     Hs = ex->template alloc<double>(static_cast<size_t>(t.nnzH));
-    tmpN = ex->template alloc<double>(static_cast<size_t>(t.N));
+    tmpN = ex->template alloc<double>(static_cast<size_t>(t.N + t.row_work()));
     dense_w = ex->template ctl_alloc<double>(static_cast<size_t>(t.nblk));
   }
   DNLP_HD void clear_dense_w() { for (i64 k = 0; k < t.nblk; ++k) dense_w[k] = 0.0; }
@@ -247,6 +247,7 @@ struct Model {
       else if (g.op == OP_PROD) sweep_prod_segment(g, x, with_h);
       else if (g.op == OP_QUAD_OVER_LIN_ROWS) sweep_qol_rows_segment(g, x, with_h);
       else if (g.op == OP_LOG_DET) sweep_logdet_segment(g, x, with_h);
+      else if (g.op == OP_MATRIX_FRAC) sweep_mfrac_segment(g, x, with_h);
       else DNLP_FAIL("row-class segment with an unknown opcode");
     }
   }
@@ -431,6 +432,32 @@ struct Model {
       tri_decode(e - r * T, false, a, b);
       const double* d = dv + r * K;
       hv[e] = -ww[r] * d[b % n + (a / n) * n] * d[a % n + (b / n) * n];
+    });
+  }
+
+  // OP_MATRIX_FRAC (lowering.py _lower_MatrixFrac; the reference's matrix_frac.py has a gradient and no second
+  // derivative): z = tr(X^T P^-1 X).  One row holds P (order n = d2, F order) and then X (n x m, F order), K = n (n + m).
+  // The rule is row_class.h mfrac_segment (mfrac_row, mfrac_d) and mfrac_h: n steps of the unpivoted elimination on the bordered matrix
+  // [[P, X], [X^T, 0]] of order N = n + m give B = inv(P), W = B X, V = B^T X and z at once.  Two maps -- the row (build
+  // the bordered matrix, sweep it, write z and the K first derivatives), Hessian entries (the packed lower triangle over
+  // the K entries, row-major).  The swept matrix waits between them behind the N entries of tmpN (TapeView::row_work()
+  // doubles: the largest N^2 of the tape, since segments are swept one after the other).  A pivot <= 0 or NaN: z, every d
+  // and every h of the segment are NaN.
+  DNLP_HD void sweep_mfrac_segment(const SegHost& g, const double* x, bool with_h) {
+    DNLP_THIS_IN_LDS(E); DNLP_PTR_IN_LDS(E, ex);
+    const i32* gidx = t.gidx;
+    const i64 K = g.d1, n = g.d2, N = K / n, T = K * (K + 1) / 2, a0b = g.a0_base, a0o = g.a0_off;
+    double* z = xz + t.N + g.zoff;
+    double* dv = dvals + g.doff;
+    double* hv = hvals + g.hoff;
+    double* sw = tmpN + t.N;
+    const double* ww = w + g.zoff;
+    ex->map(1, [=] DNLP_HD(i64) { z[0] = mfrac_segment(sw, dv, x, gidx, a0b, a0o, N, n); });
+    if (!with_h) return;
+    ex->map(T, [=] DNLP_HD(i64 e) {
+      i64 p, q;
+      tri_decode(e, false, p, q);
+      hv[e] = ww[0] * mfrac_h(sw, dv, N, n, p, q);
     });
   }
 

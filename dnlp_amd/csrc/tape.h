@@ -202,6 +202,17 @@ struct TapeView {
   i64 nfree = 0, red_depth = 0;
   i32 *def_var = nullptr, *free_idx = nullptr;
 
+  // doubles the generic sweep needs beside its N-vector (model.h tmpN): the largest bordered matrix of a matrix_frac
+  // segment, which waits there between the segment's two maps (segments are swept one after the other)
+  DNLP_HD i64 row_work() const {
+    i64 most = 0;
+    for (i64 rk = 0; rk < nrow; ++rk) {
+      const SegHost& g = segs[row_segs[rk]];
+      if (g.op == OP_MATRIX_FRAC && g.d2 > 0 && (g.d1 / g.d2) * (g.d1 / g.d2) > most) most = (g.d1 / g.d2) * (g.d1 / g.d2);
+    }
+    return most;
+  }
+
   DNLP_HD bool dense_bound() const {
     for (i64 k = 0; k < ndense; ++k) if (!dense_ptr[k]) return false;
     return true;
@@ -307,7 +318,7 @@ struct Tape : TapeView {
     std::vector<i64> fs{0}, a0b, a0o, a0l, a1b, a1o, a1l, zo, dof, ho, nn, e0, e1, e2;
     std::vector<i32> fop;
     std::vector<double> fp, fp2;
-    // OP_MATMUL (33) is elementwise-class (one unit per output entry) despite its opcode; op_is_row (34 .. 37) is the
+    // OP_MATMUL (33) is elementwise-class (one unit per output entry) despite its opcode; op_is_row (34 .. 38) is the
     // row class; 30 .. 32 are the reduction class; anything else is not a tape this library knows
     for (i64 s = 0; s < nseg; ++s) {
       const SegHost& g = h_segs[static_cast<size_t>(s)];
@@ -443,19 +454,30 @@ struct Tape : TapeView {
         // rows that share entries across rows could outnumber the N-vector the generic sweep parks in.  The front-end
         // cannot produce such a tape (the argument is one variable).
         if (mb.parks && len > 1 && 2 * rows > N) throw std::runtime_error(name + " segment with more rows than half the variables: its rows share entries");
-        if (mb.square) {
+        if (mb.square && !mb.bordered) {
           // one matrix per segment, its order in d2; the whole matrix is one wavefront's registers on the device
           if (g.d2 <= 0 || g.d2 * g.d2 != len) throw std::runtime_error(name + " segment whose row is not a square matrix: d2 * d2 != d1");
           if (rows != 1) throw std::runtime_error(name + " segment with more than one matrix: M != 1");
           if (len > kRowWaveMax) throw std::runtime_error(name + " segment with more than " + std::to_string(kRowWaveMax) + " entries: the order of a matrix ends at 45");
         }
-        if ((len <= kRowShortMax) == (lng != 0)) continue;
+        if (mb.bordered) {
+          // P of order n = d2 and X of n x m in one row: d1 = n (n + m), m >= 0; the bordered matrix of order n + m is one
+          // wavefront's registers on the device
+          if (g.d2 <= 0 || len % g.d2 != 0) throw std::runtime_error(name + " segment whose row is not n rows of n + m entries: d1 % d2 != 0");
+          if (len < g.d2 * g.d2) throw std::runtime_error(name + " segment whose row is shorter than its square matrix: d1 < d2 * d2");
+          if (rows != 1) throw std::runtime_error(name + " segment with more than one matrix: M != 1");
+          if (mb.work(len, g.d2) > kRowWaveMax)
+            throw std::runtime_error(name + " segment whose bordered matrix has more than " + std::to_string(kRowWaveMax) + " entries: (d1 / d2)^2 = " +
+                                     std::to_string(mb.work(len, g.d2)) + ", its order n + m ends at 45");
+        }
+        const i64 work = mb.work(len, g.d2);
+        if ((work <= kRowShortMax) == (lng != 0)) continue;
         i64 units;
-        if (!lng) { i64 grp = 1; while (grp < len) grp <<= 1; const i64 per = 64 / grp; units = (rows + per - 1) / per; }   // wavefronts
-        else units = len <= kRowWaveMax ? (rows + 3) / 4 : rows;                                     // workgroups of four wavefronts
+        if (!lng) { i64 grp = 1; while (grp < work) grp <<= 1; const i64 per = 64 / grp; units = (rows + per - 1) / per; }   // wavefronts
+        else units = work <= kRowWaveMax ? (rows + 3) / 4 : rows;                                    // workgroups of four wavefronts
         st.push_back(st.back() + units);
         hs.push_back(hs.back() + g.hcount);
-        us.push_back(us.back() + g.dcount);
+        us.push_back(us.back() + (mb.bordered ? work : g.dcount));
         K.push_back(len); M.push_back(rows); a0b.push_back(g.a0_base); a0o.push_back(g.a0_off);
         a1b.push_back(g.a1_base); a1o.push_back(g.a1_off);
         zo.push_back(g.zoff); dof.push_back(g.doff); ho.push_back(g.hoff); ord.push_back(g.d2);
@@ -474,6 +496,10 @@ struct Tape : TapeView {
       if (mb.op == OP_PROD && lng) {
         rt.ustart = up(us.data(), us.size());
         rt.park = ex->template alloc<double>(static_cast<size_t>(4 * rt.units + us.back()));
+      }
+      if (mb.bordered && lng) {        // the swept matrices wait here for the spread Hessian launch
+        rt.ustart = up(us.data(), us.size());
+        rt.park = ex->template alloc<double>(static_cast<size_t>(us.back()));
       }
     }
     row_tab = h_row_tab.data();

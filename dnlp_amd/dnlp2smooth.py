@@ -174,13 +174,9 @@ def _quad_over_lin_rows(atom, args):
     return _alias_arguments(atom, args, (PLAIN, Aux(nonneg=True, init=init_if_safely_positive)))
 
 
-def _log_det(atom, args):
-    """No reference rule (log_det.py has a gradient and nothing else).  Always a new variable T of the argument's shape with
-    the row T == (A + A.T) / 2 and no bounds -- a bare Variable is replaced too, like log's -- so the tape op reads n^2
-    distinct entries that are symmetric at every feasible point, where its unpivoted elimination succeeds exactly on the
-    positive definite cone (csrc/row_class.h logdet_row).  T starts at the symmetric part of A's value where its Cholesky
-    factorisation exists, otherwise at the identity."""
-    A = args[0]
+def _symmetrised(A):
+    """-> (T, row): a new variable T of A's shape with the row T == (A + A.T) / 2 and no bounds.  T starts at the symmetric
+    part of A's value where its Cholesky factorisation exists, otherwise at the identity."""
     n = A.shape[0]
     T = Variable(A.shape)
     start = np.eye(n)
@@ -192,7 +188,31 @@ def _log_det(atom, args):
         except np.linalg.LinAlgError:
             pass
     T.value = start
-    return atom.copy([T]), [T == (A + A.T) / 2]
+    return T, T == (A + A.T) / 2
+
+
+def _log_det(atom, args):
+    """No reference rule (log_det.py has a gradient and nothing else).  Always a new variable T of the argument's shape with
+    the row T == (A + A.T) / 2 and no bounds -- a bare Variable is replaced too, like log's -- so the tape op reads n^2
+    distinct entries that are symmetric at every feasible point, where its unpivoted elimination succeeds exactly on the
+    positive definite cone (csrc/row_class.h logdet_row).  T starts at the symmetric part of A's value where its Cholesky
+    factorisation exists, otherwise at the identity."""
+    T, row = _symmetrised(args[0])
+    return atom.copy([T]), [row]
+
+
+def _matrix_frac(atom, args):
+    """No reference rule (matrix_frac.py has a gradient and nothing else).  P is replaced as log_det's argument is
+    (_symmetrised); X is aliased like PLAIN -- a bare Variable stays, anything else, a constant among them, becomes
+    t == X -- so every entry of the tape row is an x index.  Rows in argument order: X's, then T's."""
+    X, P = args
+    rows = []
+    if not isinstance(X, Variable):
+        t = PLAIN.make(atom, X, 0)
+        rows.append(t == X)
+        X = t
+    T, row = _symmetrised(P)
+    return atom.copy([X, T]), rows + [row]
 
 
 def _rel_entr(atom, args):
@@ -324,6 +344,7 @@ RULES.update({
     at.QuadOverLinRows: _quad_over_lin_rows,
     at.rel_entr: _rel_entr,
     at.log_det: _log_det,
+    at.MatrixFrac: _matrix_frac,
     # rewrites
     at.kl_div: _kl_div,
     at.DivExpression: _quotient,

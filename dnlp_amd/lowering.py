@@ -50,6 +50,7 @@ OP_LOG_SUM_EXP = 34          # row class: many short (or few long) reductions, o
 OP_PROD = 35                 # row class: the same rows with the STRICT lower triangle (a product's Hessian diagonal is zero)
 OP_LOG_DET = 37              # row class: one row holding the n^2 entries of a matrix of order n (dims[2]); the full triangle over them
 ROW_WAVE_MAX = 2048          # csrc/row_class.h kRowWaveMax: the entries one wavefront holds, 32 per lane
+OP_MATRIX_FRAC = 38          # row class: one row holding P (n^2 entries, F order) then X (n m entries, F order); dims[2] = n; the full triangle
 OP_QUAD_OVER_LIN_ROWS = 36   # row class with a second argument (one denominator per row); an arrow of 2K + 1 Hessian entries per row
 
 UNARY_OPS = {
@@ -304,7 +305,7 @@ class Segment:
     hoff: int = 0
     hcount: int = 0
     aux: int = -1               # constant-matrix id (quad_form) / inner dimension (matmul)
-    dims: tuple = (0, 0, 0)     # matmul (m, k, p); row class (rows M, row length K, 0 -- log_det: the matrix order n)
+    dims: tuple = (0, 0, 0)     # matmul (m, k, p); row class (rows M, row length K, 0 -- log_det, matrix_frac: the matrix order n)
 
 
 @dataclass
@@ -807,6 +808,26 @@ class Lowerer:
             raise ValueError("log_det: a matrix of order %d has %d entries; one wavefront holds the whole matrix, at most "
                              "%d entries (order %d)." % (n, n * n, ROW_WAVE_MAX, int(np.sqrt(ROW_WAVE_MAX))))
         return self._row_class(e, "log_det", OP_LOG_DET, 0, geometry=(1, n * n, self._gather(a)), dims2=n)
+
+    def _lower_MatrixFrac(self, e):
+        """tr(X^T P^-1 X), P of order n and X n x m, is ONE row of K = n^2 + n m entries: a0[i + j n] = x index of P_ij,
+        a0[n^2 + i + c n] = x index of X_ic; dims = (1, K, n), so m = (K - n^2) / n.  With B = inv(P), W = B X, V = B^T X,
+        G = V W^T: d[i + j n] = -G_ij, d[n^2 + i + c n] = W_ic + V_ic; h: the lower triangle with its diagonal over the K
+        entries (csrc/model.h sweep_mfrac_segment gives its three kinds of entries).  The device sweeps the bordered
+        matrix [[P, X], [X^T, 0]] of order N = n + m in one wavefront's registers, hence N^2 <= ROW_WAVE_MAX."""
+        X, P = e.args
+        n = int(P.shape[0])
+        m = int(X.size) // n if n else 0
+        if n == 0 or m == 0:
+            raise ValueError("matrix_frac of an empty argument.")
+        if (n + m) ** 2 > ROW_WAVE_MAX:
+            fit = int(np.sqrt(ROW_WAVE_MAX))
+            raise ValueError("matrix_frac: P of order %d with %d column(s) of X is a bordered matrix of order %d with %d "
+                             "entries; one wavefront holds the whole bordered matrix, at most %d entries (n + m <= %d: "
+                             "order %d with one column).  A wider X can be split by columns into a sum of atoms."
+                             % (n, m, n + m, (n + m) ** 2, ROW_WAVE_MAX, fit, fit - 1))
+        a0 = np.concatenate([self._gather(P), self._gather(X)])
+        return self._row_class(e, "matrix_frac", OP_MATRIX_FRAC, 0, geometry=(1, n * (n + m), a0), dims2=n)
 
     def _lower_QuadOverLinRows(self, e):
         """Row class with two arguments: a0 as above, a1[r] = x index of row r's denominator.  d: M K entries dz_r/du_l at

@@ -1,10 +1,10 @@
 """Time per tape sweep of the row-class kernels (csrc/exec_hip_rows.h) of one atom, per shape, with and without the Hessian,
 against yardsticks measured in the same process, alternating sweep by sweep.
 
-    python tools/row_sweep_time.py --atom {log_sum_exp,prod,quad_over_lin_rows,log_det} [--tag NAME]      # on the MI355X
+    python tools/row_sweep_time.py --atom {log_sum_exp,prod,quad_over_lin_rows,log_det,matrix_frac} [--tag NAME]      # on the MI355X
 
-Writes one line per shape to profiles/log_sum_exp_sweep.jsonl, prod_sweep.jsonl, quad_over_lin_rows_sweep.jsonl or
-log_det_sweep.jsonl; with
+Writes one line per shape to profiles/log_sum_exp_sweep.jsonl, prod_sweep.jsonl, quad_over_lin_rows_sweep.jsonl,
+log_det_sweep.jsonl or matrix_frac_sweep.jsonl; with
 --tag NAME to profiles/<file>.<NAME>.jsonl instead, so that a run of another build of the library (DNLP_HIP_LIB) does not
 overwrite the current one.
 
@@ -20,7 +20,9 @@ Yardsticks.  Every atom: the elementwise sweep (sweep_flat_kernel on a unary exp
 8 read + 16 written, + 8 + 8 with the Hessian, per element).  prod also: the log_sum_exp kernels on a tape of the SAME
 (M, K).  log_det (M matrices of order n, one segment each) also: the log_sum_exp kernels on M rows of K = n^2 entries --
 the same Hessian bytes and the same spread launch; its lines also give the time of one elimination step, the sweep without
-the Hessian over n.
+the Hessian over n.  matrix_frac (M segments of P of order n and X of n x m, one segment each) also: the log_det kernels on M
+matrices of order N = n + m -- the same elimination over N steps where matrix_frac walks n, so the lines give the time per
+step of both -- and the log_sum_exp kernels on M rows of the same K = n N.
 
 Algorithmic bytes of a row sweep.  log_sum_exp, prod: 8 + 4 read per entry (x and its index), 8 written per output, per d
 entry and, with the Hessian on, per h entry (+ 8 read per row for its weight); K (K + 1) / 2 Hessian entries per row,
@@ -53,6 +55,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 # that of 16 x 4097 is 1.3e8; rows per shape are cut where they exceed ~3.4e7 entries.
 TRI_SHAPES = [(100000, 4), (100000, 10), (100000, 16), (5000, 64), (5000, 65), (500, 257), (2, 4097), (1, 8193)]
 LOGDET_SHAPES = [(1024, 3), (256, 8), (64, 16), (16, 32), (4, 45)]      # (matrices, order)
+MFRAC_SHAPES = [(1024, 3), (256, 7), (64, 15), (16, 31), (4, 44), (16, 16)]      # (segments, order n of P) ...
+MFRAC_COLS = {(1024, 3): 1, (256, 7): 1, (64, 15): 1, (16, 31): 1, (4, 44): 1, (16, 16): 16}       # ... and the columns m of X
 QOL_SHAPES = [(100000, 2), (100000, 3), (100000, 10), (100000, 16), (5000, 64), (5000, 65), (500, 257), (2, 4097)]
 WARM, REPS, BLOCKS = 20, 200, 4
 TRACE_LIMIT_S = 400                              # per rocprofv3 child
@@ -60,13 +64,15 @@ KERNELS = {"lse": ("sweep_rows_kernel", "sweep_rows_long_kernel", "sweep_rows_he
            "prod": ("sweep_prod_kernel", "sweep_prod_long_kernel", "sweep_prod_hess_kernel"),
            "qol": ("sweep_qol_kernel", "sweep_qol_long_kernel"),
            "logdet": ("sweep_logdet_kernel", "sweep_logdet_long_kernel", "sweep_logdet_hess_kernel"),
+           "mfrac": ("sweep_mfrac_kernel", "sweep_mfrac_long_kernel", "sweep_mfrac_hess_kernel"),
            "flat": ("sweep_flat_kernel",)}
 # per atom: its output file, its shapes, and the tapes of one sweep round in the order they are evaluated (the first is
 # the atom's own, the last the exp tape sized by the first one's bytes)
 ATOMS = {"log_sum_exp": ("log_sum_exp_sweep.jsonl", TRI_SHAPES, ("lse", "flat")),
          "prod": ("prod_sweep.jsonl", TRI_SHAPES, ("prod", "lse", "flat")),
          "quad_over_lin_rows": ("quad_over_lin_rows_sweep.jsonl", QOL_SHAPES, ("qol", "flat")),
-         "log_det": ("log_det_sweep.jsonl", LOGDET_SHAPES, ("logdet", "lse", "flat"))}
+         "log_det": ("log_det_sweep.jsonl", LOGDET_SHAPES, ("logdet", "lse", "flat")),
+         "matrix_frac": ("matrix_frac_sweep.jsonl", MFRAC_SHAPES, ("mfrac", "logdet", "lse", "flat"))}
 LOOP_M, LOOP_K = (100, 200, 400, 1000), 3      # (the ends are the two sizes to record; the others locate a crossing)
 LAUNCH_SEGMENTS = [(300, 3), (40, 2), (7, 16), (1000, 3), (5, 64), (64, 7), (9, 65), (3, 300), (2, 2049), (1, 4097), (11, 129), (90, 5)]
 LAUNCH_SWEEPS = 10
@@ -86,7 +92,17 @@ def exp_elements(nbytes, with_h):
 
 
 def launches(stream, K, with_h):
-    return 2 if stream in ("lse", "prod", "logdet") and K > 64 and with_h else 1
+    return 2 if stream in ("lse", "prod", "logdet", "mfrac") and K > 64 and with_h else 1
+
+
+def work(atom, stream, M, K):
+    """What decides the kernel form of `stream` at shape (M, K) of `atom`: the row length, or the entries of the matrix."""
+    if atom == "log_det":
+        return K * K
+    if atom == "matrix_frac":
+        N = K + MFRAC_COLS[(M, K)]
+        return K * N if stream == "lse" else N * N
+    return K
 
 
 def form(K):
@@ -130,6 +146,17 @@ def _row_tapes(atom, M, K):
         mats = [lr.matrix(K, 100.0, False, seed=7000 + k) for k in range(M)]
         tapes = [lq.matrices_tape(mats), lp.rows_tape([np.random.default_rng(K).standard_normal((M, K * K))], axis=1)]
         return [(_device(t[0]),) + tuple(t[1:]) for t in tapes], (lambda with_h: tri_bytes(M, K * K, with_h, False)), 0
+    if atom == "matrix_frac":                               # (M segments: P of order K, X of K x m)
+        import logdet_problems as lq
+        import logdet_reference as lr
+        import matrix_frac_problems as mq
+        import matrix_frac_reference as mr
+        m = MFRAC_COLS[(M, K)]
+        pairs = [mr.inputs_of(K, m, 100.0, False, seed=7000 + k) for k in range(M)]
+        mats = [lr.matrix(K + m, 100.0, False, seed=7000 + k) for k in range(M)]
+        tapes = [mq.segments_tape(pairs), lq.matrices_tape(mats),
+                 lp.rows_tape([np.random.default_rng(K).standard_normal((M, K * (K + m)))], axis=1)]
+        return [(_device(t[0]),) + tuple(t[1:]) for t in tapes], (lambda with_h: tri_bytes(M, K * (K + m), with_h, False)), 0
     axis = 1 if M > 1 else None
     rng = np.random.default_rng(K)
     if atom == "log_sum_exp":
@@ -200,7 +227,7 @@ def sweep_times(atom):
             got = times[(M, K, with_h)] = {s: [] for s in streams}
             for rep in range(WARM + REPS):
                 for s in streams:
-                    L = K * K if atom == "log_det" else K
+                    L = work(atom, s, M, K)
                     part = rows[pos:pos + launches(s, L, with_h)]
                     pos += len(part)
                     if len(part) != launches(s, L, with_h) or any(p[1] not in KERNELS[s] for p in part):
@@ -222,6 +249,9 @@ def shape_lines(atom):
             rec = {"M": M, "K": K, "form": form(K), "warm": WARM, "reps": REPS, "blocks": BLOCKS}
         elif atom == "log_det":
             rec = {"matrices": M, "n": K, "K": K * K, "form": form(K * K), "warm": WARM, "reps": REPS, "blocks": BLOCKS}
+        elif atom == "matrix_frac":
+            m = MFRAC_COLS[(M, K)]
+            rec = {"segments": M, "n": K, "m": m, "N": K + m, "K": K * (K + m), "form": form((K + m) ** 2), "warm": WARM, "reps": REPS, "blocks": BLOCKS}
         else:
             rec = {"part": "a", "M": M, "K": K, "form": form(K), "gathered": bool(notes[(M, K)]), "warm": WARM, "reps": REPS, "blocks": BLOCKS}
         for with_h in (False, True):
@@ -252,6 +282,17 @@ def shape_lines(atom):
                             "flat_us_" + tag: 1e6 * tf, "time_over_lse_" + tag: td / tl})
                 if not with_h:
                     rec["us_per_elimination_step"] = 1e6 * td / K
+            elif atom == "matrix_frac":
+                N = K + MFRAC_COLS[(M, K)]
+                nbytes, tm, td, tl = tri_bytes(M, K * N, with_h, False), mean["mfrac"], mean["logdet"], mean["lse"]
+                rec.update({"bytes_" + tag: nbytes, "mfrac_us_" + tag: 1e6 * tm, "mfrac_us_min_" + tag: 1e-3 * float(np.min(t["mfrac"])),
+                            "mfrac_spread_" + tag: spread(t["mfrac"]),
+                            "logdet_us_" + tag: 1e6 * td, "logdet_spread_" + tag: spread(t["logdet"]),
+                            "lse_us_" + tag: 1e6 * tl, "lse_spread_" + tag: spread(t["lse"]), "flat_us_" + tag: 1e6 * tf,
+                            "time_over_logdet_" + tag: tm / td, "time_over_lse_" + tag: tm / tl})
+                if not with_h:       # (n steps on order N against log_det's N steps on order N)
+                    rec.update({"us_per_elimination_step": 1e6 * tm / K, "logdet_us_per_elimination_step": 1e6 * td / N,
+                                "step_over_logdet_step": (tm / K) / (td / N)})
             else:
                 nbytes, tq = qol_bytes(M, K, with_h, bool(notes[(M, K)])), mean["qol"]
                 ebytes = exp_elements(nbytes, with_h) * (40 if with_h else 24)
