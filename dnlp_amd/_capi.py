@@ -68,6 +68,9 @@ class CApi:
         f("kkt_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)])
         f("kkt_mode", C.c_int, [C.c_void_p])
         f("kkt_tail_nodes", C.c_int64, [C.c_void_p])
+        if hasattr(self.lib, prefix + "kkt_probe"):      # parity-test entry: a library built before it existed still loads
+            f("kkt_probe", C.c_int, [C.c_void_p, _dbl_p, _dbl_p, C.c_double, _dbl_p, _dbl_p, _dbl_p, C.c_double, C.c_int,
+                                     _dbl_p, _dbl_p, C.POINTER(C.c_int), C.POINTER(C.c_int)])
         f("get_stats", C.c_int, [C.c_void_p, _dbl_p, C.c_int])
         f("get_log", C.c_size_t, [C.c_void_p, C.c_char_p, C.c_size_t])
         f("set_intermediate_cb", C.c_int, [C.c_void_p, INTERMEDIATE_CB, C.c_void_p])
@@ -471,6 +474,33 @@ class ProblemHandle:
     def kkt_tail_nodes(self) -> int:
         """Nodes of the dense tail of the sparse plan (0: none): such a plan is the host-driven loop's."""
         return int(self.api.kkt_tail_nodes(self.ptr))
+
+    def kkt_probe(self, x, lagrange, obj_factor, Sx, D, fixmask=None, delta_w=0.0, rhs=None):
+        """One assembly + factorisation of K = [[H + diag(Sx) + delta_w I, J^T], [J, -diag(D)]] at (x, lagrange, obj_factor)
+        by the handle's own KKT path and one plain solve per row of `rhs` (include/dnlp_hip.h dnlp_kkt_probe: no refinement,
+        no inertia loop, no retry).  Returns {"ok", "nneg", "nzero", "sol"}; `sol` is None when the factorisation failed."""
+        if not hasattr(self.api, "kkt_probe"):
+            raise RuntimeError("kkt_probe: %skkt_probe is not in the loaded library (built from older sources): rebuild it"
+                               % self.api.prefix)
+        n = self.n + self.m
+        x, Sx = self._x(x), self._x(Sx)
+        lam = self._x(lagrange) if self.m else np.zeros(1)
+        D = self._x(D) if self.m else np.zeros(1)
+        fm = None if fixmask is None else self._x(fixmask)
+        if x.size != self.n or Sx.size != self.n or (self.m and (lam.size != self.m or D.size != self.m)) or \
+                (fm is not None and fm.size != self.n):
+            raise ValueError("kkt_probe: x, Sx, fixmask have N values, lagrange and D have m")
+        R = np.zeros((0, n)) if rhs is None else np.ascontiguousarray(np.atleast_2d(np.asarray(rhs, dtype=np.float64)))
+        if R.shape[1] != n:
+            raise ValueError("kkt_probe: right-hand sides have N + m values")
+        sol = np.full(R.shape, np.nan)
+        nneg, nzero = C.c_int(), C.c_int()
+        rc = self.api.kkt_probe(self.ptr, _dp(x), _dp(lam), float(obj_factor), _dp(Sx), _dp(D), _dp(fm), float(delta_w),
+                                R.shape[0], _dp(R) if R.size else None, _dp(sol) if R.size else None,
+                                C.byref(nneg), C.byref(nzero))
+        if rc not in (0, 1):
+            raise RuntimeError("kkt_probe failed (%d): %s" % (rc, self.api.error()))
+        return {"ok": rc == 0, "nneg": int(nneg.value), "nzero": int(nzero.value), "sol": sol if rc == 0 else None}
 
     def reset_options(self):
         self.api.reset_options(self.ptr)

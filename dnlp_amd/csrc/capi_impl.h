@@ -174,6 +174,63 @@ struct ProblemT {
     ipm->intermediate_cb = intermediate_cb; ipm->intermediate_user = intermediate_user;
   }
 
+  // dnlp_kkt_probe (include/dnlp_hip.h): ONE assemble_factor and nrhs plain solves of the handle's own KKT object on a
+  // matrix the caller describes — no refinement, no inertia loop, no retry.  Tests measure the factorisation itself with it.
+  // The buffers stay with the handle (the level graphs of exec_hip.h are keyed by the solve vector's address).
+  double *pr_sx = nullptr, *pr_d = nullptr, *pr_fix = nullptr, *pr_v = nullptr;
+  int kkt_probe(const double* x, const double* lambda, double sigma, const double* Sx, const double* D, const double* fixmask,
+                double dw, int nrhs, const double* rhs, double* sol, int* nneg, int* nzero) {
+    const i64 N = model.t.N, m = model.t.m, n = N + m;
+    if (!x || !Sx || (m > 0 && (!lambda || !D)) || !nneg || !nzero || nrhs < 0 || (nrhs > 0 && (!rhs || !sol)))
+      throw std::runtime_error("dnlp_kkt_probe: a required argument is null or nrhs is negative");
+    if (opt.hessian_approximation == 1) throw std::runtime_error("dnlp_kkt_probe: needs hessian_approximation=exact");
+    ensure_ipm();
+    if (!pr_sx) {
+      pr_sx = ex.template alloc<double>(static_cast<size_t>(N));
+      pr_d = ex.template alloc<double>(static_cast<size_t>(m + 1));
+      pr_fix = ex.template alloc<double>(static_cast<size_t>(N));
+      pr_v = ex.template alloc<double>(static_cast<size_t>(n));
+    }
+    const size_t bN = sizeof(double) * static_cast<size_t>(N), bm = sizeof(double) * static_cast<size_t>(m);
+    ex.h2d(pr_sx, Sx, bN);
+    if (m) ex.h2d(pr_d, D, bm);
+    i64 nfix = 0;
+    if (fixmask) { ex.h2d(pr_fix, fixmask, bN); for (i64 j = 0; j < N; ++j) nfix += fixmask[j] != 0.0; }
+    else ex.zero(pr_fix, bN);
+    // the oracles' own sequence: dnlp_eval_jac_g, then dnlp_eval_h (unscaled; no interior-point state)
+    ex.h2d(dx, x, bN);
+    if (m) ex.h2d(dlam, lambda, bm);
+    model.sweep(dx, false);
+    model.eval_jac_after_sweep(djac);
+    model.eval_hess(dx, sigma, dlam);
+    swept = false;
+    // what a solve owns in the KKT object is put back; a demotion (kkt_dense.h: tail / paired -> Bunch-Kaufman) is the
+    // handle's real state and stays
+    const i64 keep_fixed = kkt.n_fixed;
+    const bool keep_skip = kkt.skip_hessian, was_paired = kkt.paired, was_opt = kkt.optimistic, was_tail = kkt.tail_pivoted;
+    const int keep_pf = kkt.paired_factorizations, keep_streak = kkt.optimistic_zero_streak;
+    kkt.n_fixed = nfix;
+    kkt.skip_hessian = false;
+    *nneg = *nzero = 0;
+    const bool ok = kkt.assemble_factor(model, djac, pr_sx, pr_d, pr_fix, dw, nneg, nzero);
+    kkt.n_fixed = keep_fixed;
+    kkt.skip_hessian = keep_skip;
+    if (kkt.paired == was_paired && kkt.optimistic == was_opt && kkt.tail_pivoted == was_tail) {
+      kkt.paired_factorizations = keep_pf;
+      kkt.optimistic_zero_streak = keep_streak;
+    }
+    if (ok) {
+      const size_t bn = sizeof(double) * static_cast<size_t>(n);
+      for (int k = 0; k < nrhs; ++k) {
+        ex.h2d(pr_v, rhs + static_cast<size_t>(k) * static_cast<size_t>(n), bn);
+        kkt.solve(pr_v, pr_v);
+        ex.d2h(sol + static_cast<size_t>(k) * static_cast<size_t>(n), pr_v, bn);
+      }
+    }
+    ex.sync();
+    return ok ? 0 : 1;
+  }
+
   // back to the defaults of a fresh handle (a cached handle is reused by the next solve of the same
   // problem: options of the previous call must not leak into it).  The linear-solver choice stays: it
   // is fixed once the KKT object exists.
@@ -459,7 +516,14 @@ struct ProblemT {
     if (!p->kkt_ready) return -1;                                                                    \
     return p->kkt.sparse ? 0 : p->kkt.paired ? 3 : p->kkt.paired_factorizations > 0 ? 4 : p->kkt.pivoted ? 1 : 2;                           \
   }                                                                                                  \
-  int DNLP_CAT(PFX, get_stats)(HANDLE* vp, double* s, int n) {                                         \
+  int DNLP_CAT(PFX, kkt_probe)(HANDLE* vp, const double* x, const double* lambda, double obj_factor, const double* Sx, \
+                               const double* D, const double* fixmask, double delta_w, int nrhs, const double* rhs,  \
+                               double* sol, int* nneg, int* nzero) {                                 \
+    auto* p = static_cast<DNLP_CAT(PFX, problem_t)*>(vp);                                            \
+    DNLP_TRY(if (!p) throw std::runtime_error("dnlp_kkt_probe: null handle");                        \
+             return p->kkt_probe(x, lambda, obj_factor, Sx, D, fixmask, delta_w, nrhs, rhs, sol, nneg, nzero);) \
+  }                                                                                                  \
+  int DNLP_CAT(PFX, get_stats)(HANDLE* vp, double* s, int n) {                                       \
     auto* p = static_cast<DNLP_CAT(PFX, problem_t)*>(vp);                                            \
     if (!p->ipm) return -1;                                                                          \
     const auto& st = p->ipm->stats;                                                                  \

@@ -336,6 +336,23 @@ int dnlp_ldlt_host(int device, double* A, int64_t n, int64_t ld, int32_t* ipiv, 
  * must extend at least 1 KiB past the last matrix element (128-row tiles over-read). */
 int dnlp_ldlt_device(int device, double* device_A, int64_t n, int64_t ld, int* nneg, int* nzero,
                      double* seconds, double* update_seconds);
+/* The handle's KKT path WITHOUT what the interior-point loop wraps around it: ONE assembly + factorisation and one plain
+ * solve per right-hand side of
+ *     K = [[H + diag(Sx) + delta_w I, J^T], [J, -diag(D)]]      (variables first, then constraint rows)
+ * where J and H are what dnlp_eval_jac_g(x) and dnlp_eval_h(x, obj_factor, lambda) return (unscaled, no interior-point
+ * state) and the row and column of every variable j with fixmask[j] != 0 are those of the identity (fixmask may be
+ * NULL: none).  The KKT object is the handle's own, built on first use as a solve builds it (linear_solver,
+ * sparse_dense_tail, kkt_paired, kkt_pivot_max_n are honoured; dnlp_kkt_mode afterwards says which path ran).  No
+ * iterative refinement, no inertia correction, no retry: what comes back is what the factorisation computed.
+ * rhs, sol: nrhs vectors of N + m values, one after the other.  Returns 0 when the factorisation reported success,
+ * 1 when it did not (*nneg, *nzero are written, sol is untouched), -199 on misuse (dnlp_last_error).
+ * A probe leaves nothing behind that changes a later solve — except the demotions of the KKT object, which are the
+ * handle's real state and are not hidden: a dense tail or a paired factorisation that met a zero pivot or excessive
+ * growth hands itself to Bunch-Kaufman for good, also when a probe's matrix caused it (tests: one handle per case).
+ * Host-driven handles only; the batch kernels have no such entry. */
+int dnlp_kkt_probe(dnlp_problem* p, const double* x, const double* lambda, double obj_factor, const double* Sx,
+                   const double* D, const double* fixmask, double delta_w, int nrhs, const double* rhs, double* sol,
+                   int* nneg, int* nzero);
 
 #ifdef __cplusplus
 }

@@ -385,3 +385,35 @@ extern "C" int orc_wave_plan_levels(orc_problem* vp, int32_t* out, int cap) {
     }
     return nlev;)
 }
+
+// more of the plan for the KKT probe tests (tests/kkt_problems.py).  what = 0: per level, 4 values: forward targets, rows
+// gathered by them, the longest gather, panel columns of the dense tail (0: none); returns the number of levels.
+// what = 1: per pivot block in elimination order, 2 values: its nodes (the second is -1 for a 1x1 block; variables
+// first, then N + constraint row); returns the number of blocks.  -1: no such plan; -2: out is too small.
+extern "C" long long orc_kkt_plan_detail(orc_problem* vp, int what, int64_t* out, long long cap) {
+  using namespace dnlp;
+  orc_problem_t* p = vp;
+  DNLP_TRY(
+    p->plan_linear_solver();
+    const SparsePlanHost& sp = p->sparse_plan;
+    if (what == 1) {       // (a forced-dense handle in paired mode has the plan's blocks too: kkt_dense.h takes its pairs from them)
+      if (sp.bnode.empty()) return -1;
+      const long long nb = static_cast<long long>(sp.bnode.size() / 2);
+      if (2 * nb > cap) return -2;
+      for (long long k = 0; k < 2 * nb; ++k) out[k] = sp.bnode[static_cast<size_t>(k)];
+      return nb;
+    }
+    if (!p->use_sparse) return -1;
+    const long long nlev = static_cast<long long>(sp.lev_off.size()) - 1;
+    if (4 * nlev > cap) return -2;
+    for (long long l = 0; l < nlev; ++l) {
+      const int h0 = sp.lev_f[static_cast<size_t>(l)], h1 = sp.lev_f[static_cast<size_t>(l) + 1];
+      int maxf = 0;
+      for (int h = h0; h < h1; ++h) maxf = std::max(maxf, sp.foff[static_cast<size_t>(h) + 1] - sp.foff[static_cast<size_t>(h)]);
+      out[4 * l] = h1 - h0;
+      out[4 * l + 1] = sp.foff[static_cast<size_t>(h1)] - sp.foff[static_cast<size_t>(h0)];
+      out[4 * l + 2] = maxf;
+      out[4 * l + 3] = static_cast<size_t>(l) < sp.pg_cols.size() ? sp.pg_cols[static_cast<size_t>(l)] : 0;
+    }
+    return nlev;)
+}

@@ -1,6 +1,7 @@
 """Static-pattern sparse LDL^T of the KKT system (csrc/sparse_plan.h, sparse_ldl.h) against the
-dense Bunch-Kaufman path: same optima on every golden problem, the plan's invariants, and the
-factorisation itself against numpy on assembled matrices."""
+dense Bunch-Kaufman path: same optima on every golden problem and the plan's invariants.  The
+factorisation itself — assembly, factors and unrefined solves against an independent reference on assembled
+matrices — is in test_kkt_probe_cpu.py (host build) and test_kkt_probe_gpu.py (device), through the C ABI's kkt_probe."""
 import numpy as np
 import pytest
 
@@ -178,8 +179,11 @@ def test_level_graph_replay_is_the_same_computation(gpu_required, monkeypatch):
     """The host-driven sparse factorisation / solves replay their level loops as HIP graphs
     (HipExec::replay_levels).  A replay launches the very same kernels with the same arguments, so the solve
     of a problem large enough for the chip-wide level kernels (small NMF: order 10 836, 9.5e5 update
-    triples) must land on the same point as the direct launches (the update kernels add with FP64 atomics, so
-    the two runs agree to rounding, not bit for bit)."""
+    triples) must land on the same point as the direct launches.  The level kernels gather every destination in a fixed
+    order and hold no floating-point atomics (csrc/exec_hip.h sp_update_gather*, sp_fwd_gather*): for plans without a
+    dense tail one factorisation and its solves are bit-identical with replay on and off (test_kkt_probe_gpu.py).  A plan
+    with a tail and panel products, which this problem may have, is in no bit-identity run: this comparison of whole
+    solves keeps the rounding-level tolerances it was written with."""
     import dnlp_amd as cp
     from paper_examples import PAPER
     runs = []
@@ -198,8 +202,7 @@ def test_level_graph_replay_is_the_same_computation(gpu_required, monkeypatch):
     a, b = runs
     assert a["status"] == b["status"] == 0
     assert abs(a["iterations"] - b["iterations"]) <= 2
-    # (the level kernels sum their updates with atomics: run-to-run order differs, and at the barrier's 1e-11 end
-    #  the ill-conditioned last steps carry that into the sixth digit of the large multipliers)
+    # (tolerances from the time the level kernels summed their updates with atomics; see the docstring)
     np.testing.assert_allclose(a["x"], b["x"], rtol=1e-5, atol=1e-7)
     assert abs(a["obj_val"] - b["obj_val"]) <= 1e-9 * max(1.0, abs(b["obj_val"]))
 
