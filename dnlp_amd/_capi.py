@@ -71,6 +71,10 @@ class CApi:
         if hasattr(self.lib, prefix + "kkt_probe"):      # parity-test entry: a library built before it existed still loads
             f("kkt_probe", C.c_int, [C.c_void_p, _dbl_p, _dbl_p, C.c_double, _dbl_p, _dbl_p, _dbl_p, C.c_double, C.c_int,
                                      _dbl_p, _dbl_p, C.POINTER(C.c_int), C.POINTER(C.c_int)])
+        if hasattr(self.lib, prefix + "batch_kkt_probe"):      # (the same: both libraries export it)
+            _ip = C.POINTER(C.c_int)
+            f("batch_kkt_probe", C.c_int, [C.c_void_p, C.c_int, _dbl_p, C.c_int64] + [_dbl_p] * 4 + [C.c_double, C.c_int] +
+              [_dbl_p] * 5 + [_ip] * 3)
         f("get_stats", C.c_int, [C.c_void_p, _dbl_p, C.c_int])
         f("get_log", C.c_size_t, [C.c_void_p, C.c_char_p, C.c_size_t])
         f("set_intermediate_cb", C.c_int, [C.c_void_p, INTERMEDIATE_CB, C.c_void_p])
@@ -501,6 +505,51 @@ class ProblemHandle:
         if rc not in (0, 1):
             raise RuntimeError("kkt_probe failed (%d): %s" % (rc, self.api.error()))
         return {"ok": rc == 0, "nneg": int(nneg.value), "nzero": int(nzero.value), "sol": sol if rc == 0 else None}
+
+    def batch_kkt_probe(self, data, x, lagrange, Sx, D, delta_w=0.0, rhs=None, v=None):
+        """include/dnlp_hip.h dnlp_batch_kkt_probe: per instance row of `data` (B, stride), ONE assembly + factorisation of
+        K = [[H + diag(Sx) + delta_w I, J^T], [J, -diag(D)]] at (x, lagrange) by the wavefront batch solver's kernels (the
+        host library: the same text on one host lane), one plain solve per right-hand side, a joint solve of the first two,
+        and the kernel's residual rhs - K v — no scaling, no push into the bounds, no refinement, no retry.  x, Sx: (B, N);
+        lagrange, D: (B, m); rhs: (B, nrhs, N + m); v: (B, 2 if nrhs >= 2 else 1, N + m) or None.  Returns {"sol", "sol2",
+        "res", "nneg", "nzero", "ok"} and, from the device library, the "launch" record of solve_batch."""
+        if not hasattr(self.api, "batch_kkt_probe"):
+            raise RuntimeError("batch_kkt_probe: %sbatch_kkt_probe is not in the loaded library (built from older sources): "
+                               "rebuild it" % self.api.prefix)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        B, stride = data.shape
+        n = self.n + self.m
+        arr = lambda a, w: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(B, w) if w else np.zeros((B, 1)))
+        try:
+            x, Sx, lam, D = arr(x, self.n), arr(Sx, self.n), arr(lagrange, self.m), arr(D, self.m)
+        except ValueError:
+            raise ValueError("batch_kkt_probe: x, Sx are (B, N), lagrange and D are (B, m)")
+        R = np.zeros((B, 0, n)) if rhs is None else np.ascontiguousarray(np.asarray(rhs, dtype=np.float64))
+        if R.ndim != 3 or R.shape[0] != B or R.shape[2] != n:
+            raise ValueError("batch_kkt_probe: right-hand sides are (B, nrhs, N + m)")
+        nrhs = R.shape[1]
+        nv = 2 if nrhs >= 2 else 1
+        if v is not None:
+            v = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+            if v.shape != (B, nv, n) or nrhs < 1:
+                raise ValueError("batch_kkt_probe: v is (B, %d, N + m) beside %d right-hand sides" % (nv, nrhs))
+        sol, sol2, res = np.full((B, nrhs, n), np.nan), np.full((B, 2, n), np.nan), np.full((B, 3, n), np.nan)
+        nneg, nzero, ok = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        rc = self.api.batch_kkt_probe(self.ptr, B, _dp(data), stride, _dp(x), _dp(lam), _dp(Sx), _dp(D), float(delta_w), nrhs,
+                                      _dp(R) if R.size else None, None if v is None else _dp(v), _dp(sol) if sol.size else None,
+                                      _dp(sol2), _dp(res), ip(nneg), ip(nzero), ip(ok))
+        if rc != 0:
+            raise RuntimeError("batch_kkt_probe failed (%d): %s" % (rc, self.api.error()))
+        out = {"sol": sol, "sol2": sol2 if nrhs >= 2 else None, "res": res if v is not None else None, "nneg": nneg,
+               "nzero": nzero, "ok": ok.astype(bool)}
+        if hasattr(self.api, "batch_launch_info"):
+            info = np.zeros(8, dtype=np.int32)
+            if self.api.batch_launch_info(self.ptr, info.ctypes.data_as(_i32_p)) == 0:
+                out["launch"] = {"grid": int(info[0]), "lanes": int(info[1]), "lds_mode": int(info[2]) & 3, "per_cu": int(info[3]),
+                                 "wave_form": int(info[6]), "wave_spec": bool(int(info[6]) and (int(info[2]) & 4)),
+                                 "wave_wg": bool(int(info[6]) and (int(info[2]) & 8))}
+        return out
 
     def reset_options(self):
         self.api.reset_options(self.ptr)

@@ -467,8 +467,8 @@ struct BatchRunner {
     WaveLayoutIn l;
     l.c0 = lay.c0; l.c = lay.c; l.b = lay.b; l.Jc = lay.Jc; l.G = lay.G; l.Mg = lay.Mg; l.Mw = lay.Mw; l.MJ = lay.MJ; l.MH = lay.MH;
     l.fp = lay.fp; l.fp2 = lay.fp2; l.x0 = lay.x0; l.lb = lay.lb; l.ub = lay.ub; l.cl = lay.cl; l.cu = lay.cu; l.total = lay.total;
-    const bool tail = std::getenv("DNLP_WAVE_WG_TAIL") && std::atoi(std::getenv("DNLP_WAVE_WG_TAIL")) == 1;
-    wave_wg_blk = build_wave_plan(ex, *tape, *host_plan, l, tail);
+    // (never with the register tail: that code is one wavefront's)
+    wave_wg_blk = build_wave_plan(ex, *tape, *host_plan, l, false);
     if (reinterpret_cast<const WaveHdr*>(wave_wg_blk.data())->state_doubles != h.state_doubles) { wave_wg_blk.assign(1, 0); return false; }
     DNLP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_wave_wg_blk), wave_wg_blk.size() * sizeof(i32)));
     DNLP_HIP_CHECK(hipMemcpy(d_wave_wg_blk, wave_wg_blk.data(), wave_wg_blk.size() * sizeof(i32), hipMemcpyHostToDevice));
@@ -777,12 +777,12 @@ struct BatchRunner {
 
   void solve_impl(int batch, const double* data, const double* theta, const IpmOptions& opt, double* x_out, double* obj_out,
                   double* multg_out, double* zl_out, double* zu_out, int* status_out, int* iters_out, int* nfact_out,
-                  double* seconds, double* times_out, bool allow_wave = true) {
+                  double* seconds, double* times_out, bool allow_wave = true, const WaveProbe* probe = nullptr) {
     const i64 stride = in_stride;
     if (batch < 0) throw std::runtime_error("batch solve: negative instance count");
     if (batch == 0) {                 // an empty launch (an empty shard of a sharded batch) is a launch of nothing
       if (seconds) *seconds = 0.0;
-      ws_batch = 0;
+      if (!probe) ws_batch = 0;
       last_grid = 0; last_wave = 0; last_wave_refused = 0;
       if (!rows_nested) { rows_batch = 0; rows_width = 4 + static_cast<int>(tape->N); }
       return;
@@ -844,8 +844,16 @@ struct BatchRunner {
     const int wave_env = std::getenv("DNLP_BATCH_WAVE") ? std::atoi(std::getenv("DNLP_BATCH_WAVE")) : 1;
     bool take_wave = allow_wave && wave_env != 0 && wave_prepare();
     if (take_wave && wave_env != 2) { int nw = 0, sl = 0, pl = 0; wave_form(nw, sl, pl); take_wave = sl != 0 || wave_wg_prepare(batch); }
+    if (probe && !take_wave) {        // (probe_wave: the wavefront solver's kernels or nothing)
+      probe_why = !wave_why.empty() ? wave_why
+                  : wave_env == 0   ? std::string("DNLP_BATCH_WAVE=0 keeps every launch on the generic kernel")
+                                    : std::string("a launch of this size takes the generic kernel for this template (its state exceeds LDS and the "
+                                                  "workgroup-per-instance kernel is not taken: DNLP_BATCH_WAVE=2 or DNLP_WAVE_SPEC=1)");
+      release();
+      return;
+    }
     if (take_wave) {
-      solve_wave(a, batch, data, theta, opt, x_out, obj_out, multg_out, zl_out, zu_out, status_out, iters_out, nfact_out, seconds, times_out);
+      solve_wave(a, batch, data, theta, opt, x_out, obj_out, multg_out, zl_out, zu_out, status_out, iters_out, nfact_out, seconds, times_out, probe);
       return;
     }
     const i64 n = t.N + t.m, ld = (n + 7) / 8 * 8;
@@ -1167,6 +1175,24 @@ struct BatchRunner {
       default: return wave_static_lds<1, true, true>();
     }
   }
+  // dnlp_batch_kkt_probe (include/dnlp_hip.h): WaveIpm::probe on every instance through the kernel form that solve_wave
+  // picks for a launch of this size under the same environment switches — the same code path up to the launch, which takes
+  // the probe entry point of that form; the launch record (last_wave, last_lds_mode, ...) is the solve's.  `io`: HOST
+  // pointers (wave_args.h WaveProbe).  0, or -2 with probe_why when the wavefront solver does not take the template.
+  std::string probe_why;
+  hipFunction_t wave_spec_probe_fn = nullptr, wave_wg_probe_fn = nullptr;
+  int probe_wave(int batch, const double* data, i64 stride, const IpmOptions& opt, const WaveProbe& io) {
+    if (stride != in_stride) throw std::runtime_error("dnlp_batch_kkt_probe: instance stride does not match the tape");
+    probe_why.clear();
+    solve_impl(batch, data, nullptr, opt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, &io);
+    return probe_why.empty() ? 0 : -2;
+  }
+  template <int NW, bool SL, bool PL>
+  void launch_probe(const WaveArgs& w, int grid, unsigned lds, hipStream_t stream) {
+    const void* k = reinterpret_cast<const void*>(wave_probe_kernel<NW, SL, PL>);
+    DNLP_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    hipLaunchKernelGGL((wave_probe_kernel<NW, SL, PL>), dim3(static_cast<unsigned>(grid)), dim3(64 * NW), lds, stream, w);
+  }
   void wave_form(int& nw, int& sl, int& pl) {
     if (wf_nw > 0 && !std::getenv("DNLP_WAVE_FORM")) { nw = wf_nw; sl = wf_sl; pl = wf_pl; return; }
     const WaveHdr& h = *reinterpret_cast<const WaveHdr*>(wave_blk.data());
@@ -1217,7 +1243,7 @@ struct BatchRunner {
   }
   void solve_wave(const BatchArgs& a, int batch, const double* data, const double* theta, const IpmOptions& opt, double* x_out, double* obj_out,
                   double* multg_out, double* zl_out, double* zu_out, int* status_out, int* iters_out, int* nfact_out,
-                  double* seconds, double* times_out) {
+                  double* seconds, double* times_out, const WaveProbe* probe = nullptr) {
     const Tape<HipExec>& t = *tape;
     const WaveHdr& h = *reinterpret_cast<const WaveHdr*>(wave_blk.data());
     if (this->ncu == 0) {
@@ -1305,16 +1331,61 @@ struct BatchRunner {
     else if (!sl) w.state = dalloc<double>(static_cast<size_t>(grid) * static_cast<size_t>(nw) * static_cast<size_t>(h.state_doubles));
     w.park_doubles = wave_park_doubles(t.N, t.m);
     w.park = dalloc<double>(static_cast<size_t>(grid) * static_cast<size_t>(wg ? 1 : spec ? wave_spec_nw : nw) * static_cast<size_t>(w.park_doubles));
-    w.x_out = dalloc<double>(static_cast<size_t>(batch) * t.N);
-    w.obj_out = dalloc<double>(static_cast<size_t>(batch));
-    w.multg_out = multg_out ? dalloc<double>(static_cast<size_t>(batch) * t.m) : nullptr;
-    w.zl_out = zl_out ? dalloc<double>(static_cast<size_t>(batch) * t.N) : nullptr;
-    w.zu_out = zu_out ? dalloc<double>(static_cast<size_t>(batch) * t.N) : nullptr;
-    w.status_out = dalloc<int>(static_cast<size_t>(batch));
-    w.iters_out = dalloc<int>(static_cast<size_t>(batch));
-    w.nfact_out = dalloc<int>(static_cast<size_t>(batch));
-    w.times_out = times_out ? dalloc<double>(4 * static_cast<size_t>(batch)) : nullptr;
-    const bool warm = ws_batch == batch && opt.warm_start;
+    if (!probe) {
+      w.x_out = dalloc<double>(static_cast<size_t>(batch) * t.N);
+      w.obj_out = dalloc<double>(static_cast<size_t>(batch));
+      w.multg_out = multg_out ? dalloc<double>(static_cast<size_t>(batch) * t.m) : nullptr;
+      w.zl_out = zl_out ? dalloc<double>(static_cast<size_t>(batch) * t.N) : nullptr;
+      w.zu_out = zu_out ? dalloc<double>(static_cast<size_t>(batch) * t.N) : nullptr;
+      w.status_out = dalloc<int>(static_cast<size_t>(batch));
+      w.iters_out = dalloc<int>(static_cast<size_t>(batch));
+      w.nfact_out = dalloc<int>(static_cast<size_t>(batch));
+      w.times_out = times_out ? dalloc<double>(4 * static_cast<size_t>(batch)) : nullptr;
+    }
+    // a probe launch: its inputs in one device array, its outputs in another, the block that names them in a third
+    // (a warm start set for the next solve stays set, and so does the order that solve will take its instances in)
+    WaveProbe dpr;
+    double* d_pout = nullptr;
+    int* d_pint = nullptr;
+    size_t pr_out = 0;
+    if (probe) {
+      const size_t B = static_cast<size_t>(batch), N = static_cast<size_t>(t.N), m = static_cast<size_t>(t.m), nn = N + m;
+      const size_t R = static_cast<size_t>(probe->nrhs), nv = probe->v ? (R >= 2 ? 2 : 1) : 0;
+      const size_t sz[6] = {B * N, B * m, B * N, B * m, B * R * nn, B * nv * nn};
+      const double* src[6] = {probe->x, probe->lam, probe->Sx, probe->D, probe->rhs, probe->v};
+      size_t pr_in = 0;
+      for (size_t q : sz) pr_in += q;
+      pr_out = B * (R + 2 + 3) * nn;
+      double* d_pin = dalloc<double>(pr_in);
+      d_pout = dalloc<double>(pr_out);
+      d_pint = dalloc<int>(3 * B);
+      WaveProbe* d_pr = dalloc<WaveProbe>(1);
+      const double* at[6];
+      size_t o = 0;
+      for (int q = 0; q < 6; ++q) {
+        at[q] = d_pin + o;
+        if (sz[q]) DNLP_HIP_CHECK(hipMemcpyAsync(d_pin + o, src[q], sz[q] * sizeof(double), hipMemcpyHostToDevice, stream));
+        o += sz[q];
+      }
+      DNLP_HIP_CHECK(hipMemsetAsync(d_pout, 0, pr_out * sizeof(double), stream));
+      DNLP_HIP_CHECK(hipMemsetAsync(d_pint, 0, 3 * B * sizeof(int), stream));
+      dpr.x = at[0]; dpr.lam = at[1]; dpr.Sx = at[2]; dpr.D = at[3]; dpr.rhs = at[4]; dpr.v = nv ? at[5] : nullptr;
+      dpr.dw = probe->dw; dpr.nrhs = probe->nrhs;
+      dpr.sol = d_pout; dpr.sol2 = d_pout + B * R * nn; dpr.res = d_pout + B * (R + 2) * nn;
+      dpr.nneg = d_pint; dpr.nzero = d_pint + B; dpr.ok = d_pint + 2 * B;
+      DNLP_HIP_CHECK(hipMemcpyAsync(d_pr, &dpr, sizeof(WaveProbe), hipMemcpyHostToDevice, stream));
+      DNLP_HIP_CHECK(hipStreamSynchronize(stream));          // (dpr is a local of this call)
+      w.probe = d_pr;
+      if (wg && !wave_wg_probe_fn) {
+        wave_wg_probe_fn = wave_wg.get("dnlp_wave_wg_probe_kernel");
+        if (!wave_wg_probe_fn || !wave_wg.fits(nw, wave_wg_probe_fn)) { wave_wg_probe_fn = nullptr; throw std::runtime_error("dnlp_batch_kkt_probe: the workgroup-per-instance kernel's probe entry point is missing or does not fit its register budget"); }
+      }
+      if (spec && !wave_spec_probe_fn) {
+        wave_spec_probe_fn = wave_spec.get("dnlp_wave_spec_probe_kernel");
+        if (!wave_spec_probe_fn || !wave_spec.fits(wave_spec_nw, wave_spec_probe_fn)) { wave_spec_probe_fn = nullptr; throw std::runtime_error("dnlp_batch_kkt_probe: the per-template kernel's probe entry point is missing or does not fit its register budget"); }
+      }
+    }
+    const bool warm = !probe && ws_batch == batch && opt.warm_start;
     std::vector<double> keep_g, keep_l, keep_u;
     if (warm) {
       double* g = dalloc<double>(h_ws_g.size());
@@ -1326,7 +1397,7 @@ struct BatchRunner {
       w.ws_g = g; w.ws_l = l; w.ws_u = u;
       keep_g = h_ws_g; keep_l = h_ws_l; keep_u = h_ws_u;
     }
-    ws_batch = 0;
+    if (!probe) ws_batch = 0;
     w.next = dalloc<int>(1);
     DNLP_HIP_CHECK(hipMemsetAsync(w.next, 0, sizeof(int), stream));
 #ifdef DNLP_WAVE_PROF
@@ -1341,7 +1412,7 @@ struct BatchRunner {
     const uint64_t key = theta ? rows_hash(theta, static_cast<size_t>(batch) * static_cast<size_t>(aff_P))
                                : rows_hash(data, static_cast<size_t>(batch) * static_cast<size_t>(in_stride));
     last_order_lpt = false;
-    if (static_cast<int>(prev_iters.size()) == batch && key == prev_key && batch > grid * (wg ? 1 : nw) && !std::getenv("DNLP_BATCH_FIFO")) {
+    if (!probe && static_cast<int>(prev_iters.size()) == batch && key == prev_key && batch > grid * (wg ? 1 : nw) && !std::getenv("DNLP_BATCH_FIFO")) {
       last_order_lpt = true;
       std::vector<int> ord(static_cast<size_t>(batch));
       for (int k = 0; k < batch; ++k) ord[static_cast<size_t>(k)] = k;
@@ -1364,7 +1435,28 @@ struct BatchRunner {
     DNLP_HIP_CHECK(hipEventCreate(&e0));
     DNLP_HIP_CHECK(hipEventCreate(&e1));
     DNLP_HIP_CHECK(hipEventRecord(e0, stream));
-    if (wg) {
+    if (probe && wg) {
+      void* kargs[] = {&w};
+      DNLP_HIP_CHECK(hipModuleLaunchKernel(wave_wg_probe_fn, static_cast<unsigned>(grid), 1, 1, static_cast<unsigned>(64 * nw), 1, 1, 0, stream, kargs, nullptr));
+    } else if (probe && spec) {
+      void* kargs[] = {&w};
+      DNLP_HIP_CHECK(hipModuleLaunchKernel(wave_spec_probe_fn, static_cast<unsigned>(grid), 1, 1, static_cast<unsigned>(64 * nw), 1, 1, 0, stream, kargs, nullptr));
+    } else if (probe) switch (form) {
+      case 811: launch_probe<8, true, true>(w, grid, lds, stream); break;
+      case 711: launch_probe<7, true, true>(w, grid, lds, stream); break;
+      case 611: launch_probe<6, true, true>(w, grid, lds, stream); break;
+      case 511: launch_probe<5, true, true>(w, grid, lds, stream); break;
+      case 411: launch_probe<4, true, true>(w, grid, lds, stream); break;
+      case 311: launch_probe<3, true, true>(w, grid, lds, stream); break;
+      case 211: launch_probe<2, true, true>(w, grid, lds, stream); break;
+      case 111: launch_probe<1, true, true>(w, grid, lds, stream); break;
+      case 410: launch_probe<4, true, false>(w, grid, lds, stream); break;
+      case 310: launch_probe<3, true, false>(w, grid, lds, stream); break;
+      case 210: launch_probe<2, true, false>(w, grid, lds, stream); break;
+      case 110: launch_probe<1, true, false>(w, grid, lds, stream); break;
+      case 400: launch_probe<4, false, false>(w, grid, lds, stream); break;
+      default: throw std::runtime_error("wavefront solver: no such launch form");
+    } else if (wg) {
       void* kargs[] = {&w};
       DNLP_HIP_CHECK(hipModuleLaunchKernel(wave_wg.fn, static_cast<unsigned>(grid), 1, 1, static_cast<unsigned>(64 * nw), 1, 1, 0, stream, kargs, nullptr));
     } else if (spec) {
@@ -1395,6 +1487,19 @@ struct BatchRunner {
     hipEventDestroy(e1);
     double total_sec = 1e-3 * ms;
     mark("wave kernel done");
+    if (probe) {
+      const size_t B = static_cast<size_t>(batch), nn = static_cast<size_t>(t.N + t.m), R = static_cast<size_t>(probe->nrhs);
+      auto get = [&](void* hp, const void* d, size_t bytes) { if (hp && bytes) DNLP_HIP_CHECK(hipMemcpy(hp, d, bytes, hipMemcpyDeviceToHost)); };
+      get(probe->sol, dpr.sol, B * R * nn * sizeof(double));
+      if (R >= 2) get(probe->sol2, dpr.sol2, B * 2 * nn * sizeof(double));
+      if (dpr.v) get(probe->res, dpr.res, B * 3 * nn * sizeof(double));
+      get(probe->nneg, dpr.nneg, B * sizeof(int));
+      get(probe->nzero, dpr.nzero, B * sizeof(int));
+      get(probe->ok, dpr.ok, B * sizeof(int));
+      release();
+      if (seconds) *seconds = total_sec;
+      return;
+    }
     auto down = [&](void* hp, const void* d, size_t bytes) { if (hp && bytes) DNLP_HIP_CHECK(hipMemcpy(hp, d, bytes, hipMemcpyDeviceToHost)); };
     std::vector<int> st_local;
     int* st_host = status_out;

@@ -255,6 +255,27 @@ int dnlp_batch_result_rows(dnlp_problem* vp, const double** rows, int64_t* n_row
     return 0;)
 }
 
+int dnlp_batch_kkt_probe(dnlp_problem* vp, int batch, const double* data, int64_t stride, const double* x, const double* lambda,
+                         const double* Sx, const double* D, double delta_w, int nrhs, const double* rhs, const double* v, double* sol,
+                         double* sol2, double* res, int* nneg, int* nzero, int* ok) {
+  dnlp_problem_t* p = vp;
+  DNLP_TRY(
+    if (!p) throw std::runtime_error("dnlp_batch_kkt_probe: null handle");
+    BatchRunner& r = *batch_runner(p);
+    const bool rows = r.tape->m > 0;
+    if (batch < 0 || nrhs < 0 || (batch > 0 && (!data || !x || !Sx || (rows && (!lambda || !D)) || !nneg || !nzero || !ok ||
+                                                (nrhs > 0 && (!rhs || !sol)) || (nrhs >= 2 && !sol2) || (v && (!res || nrhs < 1)))))
+      throw std::runtime_error("dnlp_batch_kkt_probe: a required argument is null, or batch or nrhs is negative, or v is given without a right-hand side");
+    if (stride != r.in_stride) throw std::runtime_error("dnlp_batch_kkt_probe: instance stride does not match the tape");
+    if (p->opt.hessian_approximation == 1) throw std::runtime_error("dnlp_batch_kkt_probe: needs hessian_approximation=exact");
+    p->ex.sync();
+    WaveProbe io;
+    io.x = x; io.lam = lambda; io.Sx = Sx; io.D = D; io.rhs = rhs; io.v = v; io.dw = delta_w; io.nrhs = nrhs;
+    io.sol = sol; io.sol2 = sol2; io.res = res; io.nneg = nneg; io.nzero = nzero; io.ok = ok;
+    if (r.probe_wave(batch, data, stride, p->opt, io) != 0) { dnlp::tls_error() = "dnlp_batch_kkt_probe: the wavefront solver does not take this launch: " + r.probe_why; return -2; }
+    return 0;)
+}
+
 int dnlp_batch_launch_info(dnlp_problem* vp, int32_t* out8) {
   dnlp_problem_t* p = vp;
   DNLP_TRY(

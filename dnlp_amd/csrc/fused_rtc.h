@@ -270,9 +270,11 @@ struct RtcKernel {
   // does a workgroup of `waves` wavefronts of the loaded entry point fit a compute unit's register files?  (gfx950: 512
   // unified registers per lane and SIMD, four SIMDs: ceil(waves / 4) wavefronts share one.)  A launch that does not fit
   // aborts the queue (INVALID_ISA), so the callers that choose their own workgroup width ask first.
-  bool fits(int waves) const {
+  bool fits(int waves) const { return fits(waves, fn); }
+  // ... of another entry point of the module (get())
+  bool fits(int waves, hipFunction_t f) const {
     int regs = 0;
-    if (!fn || hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, fn) != hipSuccess) return false;
+    if (!f || hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, f) != hipSuccess) return false;
     return regs * ((waves + 3) / 4) <= 512;
   }
   // further entry points of the same module (nullptr when missing)

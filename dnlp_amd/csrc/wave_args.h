@@ -6,6 +6,27 @@
 
 namespace dnlp {
 
+// What a PROBE launch reads and writes (wave_ipm.h WaveIpm::probe; include/dnlp_hip.h dnlp_batch_kkt_probe), batch-major.
+// n = N + m; nv = 2 when nrhs >= 2, else 1.  One block in device memory: the argument block of a solve launch carries one
+// null pointer for it and nothing else.
+struct WaveProbe {
+  const double* x = nullptr;         // batch x N: the point
+  const double* lam = nullptr;       // batch x m: the multipliers of the constraint rows
+  const double* Sx = nullptr;        // batch x N
+  const double* D = nullptr;         // batch x m
+  const double* rhs = nullptr;       // batch x nrhs x n
+  const double* v = nullptr;         // batch x nv x n: the vectors of the residual passes (null: none)
+  double dw = 0.0;
+  int nrhs = 0;
+  int pad = 0;
+  double* sol = nullptr;             // batch x nrhs x n: one plain solve each
+  double* sol2 = nullptr;            // batch x 2 x n: right-hand sides 0 and 1 solved jointly (nrhs >= 2)
+  double* res = nullptr;             // batch x 3 x n: rhs 0 - K v 0 alone; (rhs 0 - K v 0, rhs 1 - K v 1) in one pass (nrhs >= 2)
+  int* nneg = nullptr;               // batch
+  int* nzero = nullptr;              // batch
+  int* ok = nullptr;                 // batch: the factorisation met no NaN
+};
+
 struct WaveArgs {
   const i32* blk = nullptr;          // the plan block (device memory)
   const int16_t* blk16 = nullptr;    // ... narrowed to 16 bits (null when an entry does not fit)
@@ -28,6 +49,7 @@ struct WaveArgs {
   int* next = nullptr;
   const int* order = nullptr;
   unsigned long long* prof = nullptr;   // kWaveProfSlots + 1 counters of a -DDNLP_WAVE_PROF build (last: iterations)
+  const WaveProbe* probe = nullptr;     // a probe launch's inputs and outputs (device memory); null in a solve launch
 };
 
 }  // namespace dnlp

@@ -132,4 +132,59 @@ __global__ void __launch_bounds__(64 * NW) wave_batch_kernel(WaveArgs a) {
   }
 }
 
+// The probe launch (wave_ipm.h WaveIpm::probe; a.probe: wave_args.h WaveProbe): an entry point of its own — the solve kernel
+// above has no branch for it — with the solve kernel's staging of the plan, its layout() and its out-of-line phase functions
+// (the same lane policy, so the same instantiations); W::probe stands where W::solve stands.
+template <int NW, bool STATE_LDS, bool PLAN_LDS>
+__global__ void __launch_bounds__(64 * NW) wave_probe_kernel(WaveArgs a) {
+  extern __shared__ __align__(16) char w_lds[];
+  using P = WaveLanesT<STATE_LDS, PLAN_LDS, (NW > 4)>;
+  using W = WaveIpm<P>;
+  using WState = typename W::WState;
+  using WD = typename P::D;
+  using WI = typename P::I;
+  __shared__ __align__(16) char s_state[NW][(sizeof(WState) + 15) & ~static_cast<size_t>(15)];
+  __shared__ int s_inst[NW];
+  const int wave = static_cast<int>(threadIdx.x >> 6), lane = static_cast<int>(threadIdx.x & 63u);
+  char* pool = w_lds;
+  WI* blk;
+  if constexpr (PLAN_LDS) {
+    DNLP_WLDS int16_t* dst = (DNLP_WLDS int16_t*)pool;
+    for (int k = static_cast<int>(threadIdx.x); k < a.blk_ints; k += 64 * NW) dst[k] = static_cast<int16_t>(a.blk[k]);
+    blk = (WI*)dst;
+    pool += (static_cast<size_t>(a.blk_ints) * 2 + 15) & ~static_cast<size_t>(15);
+    __syncthreads();
+  } else if constexpr (STATE_LDS) {
+    blk = (WI*)a.blk16;
+  } else {
+    blk = (WI*)a.blk;
+  }
+  WD* base;
+  if constexpr (STATE_LDS) base = (WD*)(pool + static_cast<size_t>(wave) * static_cast<size_t>(a.state_doubles) * 8);
+  else base = (WD*)(a.state + (static_cast<size_t>(blockIdx.x) * NW + wave) * static_cast<size_t>(a.state_doubles));
+  typename W::WS* S = (typename W::WS*)s_state[wave];
+  W::layout(S, reinterpret_cast<const WaveHdr*>(a.blk), blk, base);
+  wave_sync();
+  while (true) {
+    if (lane == 0) s_inst[wave] = atomicAdd(a.next, 1);
+    wave_sync();
+    const int inst = s_inst[wave];
+    wave_sync();
+    if (inst >= a.batch) break;
+    for (i64 k = lane; k < a.state_doubles; k += 64) base[k] = 0.0;
+    S->row = (WG*)(a.rows + static_cast<i64>(inst) * a.row_doubles);
+    S->park = a.park + (static_cast<i64>(blockIdx.x) * NW + wave) * a.park_doubles;
+    S->ws_g = S->ws_l = S->ws_u = nullptr;
+    S->fallback_max_n = a.fallback_max_n;
+    S->opt = a.opt;
+    S->factorizations = 0;
+#ifdef DNLP_WAVE_PROF
+    for (int k = 0; k < kWaveProfSlots; ++k) S->prof[k] = 0ull;
+#endif
+    wave_sync();
+    W::probe(S, a.probe, inst);
+    wave_sync();
+  }
+}
+
 }  // namespace dnlp

@@ -19,6 +19,7 @@
 #pragma once
 #ifndef DNLP_RTC
 #include "ipm_core.h"
+#include "wave_args.h"
 #include "wave_plan.h"
 #endif
 
@@ -2736,6 +2737,90 @@ struct WaveIpm {
     S->acceptable_count = 0;
     (void)check_convergence(S, error(S, 0.0));
     S->status = Solve_Succeeded;
+  }
+
+  // The factorisation measured on its own (include/dnlp_hip.h dnlp_batch_kkt_probe; wave_args.h WaveProbe): what a whole
+  // solve repairs — solve_refined refines on the unfactored operator, the inertia loop regularises again — is returned as it
+  // comes out.  Set up as begin() sets up, WITHOUT scaling (sf = sg = 1), bound relaxation or a push into the bounds; the
+  // given point and multipliers; the evaluation calls of a solve in its order; ONE assemble_factor on the given Sx, D and
+  // delta_w (no inertia loop, no retry); one plain solve per right-hand side, one joint solve of the first two, and the
+  // one-pass residual rhs - K v alone and for two systems.  The arrays are those the solve itself hands to these functions
+  // (a policy that types the right-hand sides by where they live — wave_wg_kernel.h — sees the cases it knows).
+  DNLP_WFN DNLP_HD static void probe(WS* S, const WaveProbe* pio, int inst) {
+    const WaveProbe io = *pio;
+    const int N = WK(N), m = WK(m), n = N + m;
+    const double inf = S->opt.nlp_inf, dw = io.dw;
+    const i64 at = static_cast<i64>(inst);
+    {
+      WG *lb = S->row + WK(l_lb), *ub = S->row + WK(l_ub), *cl = S->row + WK(l_cl), *cu = S->row + WK(l_cu);
+      const double *px = io.x + at * N, *pl = io.lam + at * m, *psx = io.Sx + at * N, *pd = io.D + at * m;
+      WD *l = WV(xL), *u = WV(xU), *sl = WV(sL), *su = WV(sU), *sgp = WV(sg), *xx = WV(x), *yy = WV(y), *fm = WV(fixm), *eq = WV(eq),
+         *sx = WV(Sx), *dd = WV(Dd);
+      W_FOR(j, N) {
+        const double a = lb[j], b = ub[j];
+        const double lj = a <= -inf ? -kInf : a, uj = b >= inf ? kInf : b;
+        const bool fx = lj == uj;
+        l[j] = fx ? -kInf : lj; u[j] = fx ? kInf : uj;
+        fm[j] = fx ? 1.0 : 0.0;
+        xx[j] = px[j];
+        sx[j] = psx[j];
+      }
+      W_FOR(i, m) {
+        const double a = cl[i] <= -inf ? -kInf : cl[i], b = cu[i] >= inf ? kInf : cu[i];
+        sl[i] = a; su[i] = b;
+        eq[i] = (a == b) ? 1.0 : 0.0;
+        sgp[i] = 1.0;
+        yy[i] = pl[i];
+        dd[i] = pd[i];
+      }
+      P::sync();
+    }
+    S->sf = 1.0;
+    S->nb_cache = -1;
+    S->initialized = false;
+    S->factorizations = 0;
+    (void)eval_fg(S, WV(x), S->f, WV(g));
+    eval_derivs(S);
+    eval_hessian(S);
+    int nneg = 0, nzero = 0;
+    const bool ok = assemble_factor(S, WV(Sx), WV(Dd), dw, false, &nneg, &nzero);
+    if (P::lane() == 0) { io.nneg[at] = nneg; io.nzero[at] = nzero; io.ok[at] = ok ? 1 : 0; }
+    WD *rhs = WV(rhs), *sol = WV(sol), *res = WV(res), *rhs2 = WDIR(2, 3), *sol2 = WDIR(2, 0), *res2 = WDIR(2, 4);
+    const int nrhs = io.nrhs;
+    const double* R = io.rhs + at * nrhs * n;
+    for (int k = 0; k < nrhs; ++k) {
+      W_FOR(i, n) rhs[i] = R[static_cast<i64>(k) * n + i];
+      P::sync();
+      kkt_solve(S, rhs, sol);
+      double* o = io.sol + (at * nrhs + k) * n;
+      W_FOR(i, n) o[i] = sol[i];
+      P::sync();
+    }
+    if (nrhs >= 2) {
+      W_FOR(i, n) { rhs[i] = R[i]; rhs2[i] = R[n + i]; }
+      P::sync();
+      kkt_solve(S, rhs, sol, rhs2, sol2);
+      double* o = io.sol2 + at * 2 * n;
+      W_FOR(i, n) { o[i] = sol[i]; o[n + i] = sol2[i]; }
+      P::sync();
+    }
+    if (io.v && nrhs >= 1) {
+      const double* V = io.v + at * (nrhs >= 2 ? 2 : 1) * n;
+      double* o = io.res + at * 3 * n;
+      W_FOR(i, n) { rhs[i] = R[i]; sol[i] = V[i]; }
+      P::sync();
+      double en, sn;
+      kkt_residual(S, sol, dw, rhs, res, en, sn);
+      W_FOR(i, n) o[i] = res[i];
+      P::sync();
+      if (nrhs >= 2) {
+        W_FOR(i, n) { rhs2[i] = R[n + i]; sol2[i] = V[n + i]; }
+        P::sync();
+        (void)kkt_residual2(S, dw, sol, rhs, res, sol2, rhs2, res2);
+        W_FOR(i, n) { o[n + i] = res[i]; o[2 * n + i] = res2[i]; }
+        P::sync();
+      }
+    }
   }
 
   // Ipm::solve (the retry ladder included)

@@ -138,3 +138,41 @@ extern "C" __global__ void __launch_bounds__(64 * wspec::kNW) dnlp_wave_spec_ker
     wave_sync();
   }
 }
+
+// The probe launch (wave_ipm.h WaveIpm::probe; a.probe: wave_args.h WaveProbe): an entry point of its own beside the solve
+// kernel — the same staging of the tables, the same shares, the same out-of-line phase functions.
+extern "C" __global__ void __launch_bounds__(64 * wspec::kNW) dnlp_wave_spec_probe_kernel(dnlp::WaveArgs a) {
+  using namespace dnlp;
+  using P = WaveLanesSpec;
+  using W = WaveIpm<P>;
+  using WD = typename P::D;
+  const int wave = static_cast<int>(threadIdx.x >> 6), lane = static_cast<int>(threadIdx.x & 63u);
+  if constexpr (wspec::kTabGlobal) {
+    if (threadIdx.x == 0) { g_wspec_plan_g = (WGlbI16*)a.blk16; g_wspec_gen_g = (DNLP_WGLB const unsigned*)a.gen; }
+  } else {
+    for (int k = static_cast<int>(threadIdx.x); k < wspec::kPlanInts; k += static_cast<int>(blockDim.x)) g_wspec_plan[k] = static_cast<int16_t>(a.blk[k]);
+    for (int k = static_cast<int>(threadIdx.x); k < wspec::kGenWords; k += static_cast<int>(blockDim.x)) g_wspec_gen[k] = a.gen[k];
+  }
+  __syncthreads();
+  typename W::WS* S = (typename W::WS*)g_wspec_share[wave].rec;
+  WD* base = (WD*)g_wspec_share[wave].vec;
+  while (true) {
+    if (lane == 0) g_wspec_inst[wave] = atomicAdd(a.next, 1);
+    wave_sync();
+    const int inst = g_wspec_inst[wave];
+    wave_sync();
+    if (inst >= a.batch) break;
+    for (int k = lane; k < wspec::kStateDoubles; k += 64) base[k] = 0.0;
+    S->row = (WG*)(a.rows + static_cast<i64>(inst) * a.row_doubles);
+    S->park = a.park + (static_cast<i64>(blockIdx.x) * wspec::kNW + wave) * a.park_doubles;
+    S->ws_g = S->ws_l = S->ws_u = nullptr;
+    S->fallback_max_n = a.fallback_max_n;
+    S->opt = a.opt;
+#ifdef DNLP_WAVE_PROF
+    for (int k = 0; k < kWaveProfSlots; ++k) S->prof[k] = 0ull;
+#endif
+    wave_sync();
+    W::probe(S, a.probe, inst);
+    wave_sync();
+  }
+}

@@ -224,3 +224,45 @@ extern "C" __global__ void __launch_bounds__(wspec::kWgBound) dnlp_wave_wg_kerne
   __syncthreads();
   dnlp_wave_wg_main();
 }
+
+// The probe launch (wave_ipm.h WaveIpm::probe; a.probe: wave_args.h WaveProbe): an entry point of its own beside the solve
+// kernel, built the same way — the arguments staged in LDS, the body a function of its own — over the same slab, LDS
+// ranges, staged tables, windows and out-of-line phase functions.
+__device__ __attribute__((noinline)) static void dnlp_wave_wg_probe_main() {
+  using namespace dnlp;
+  const DNLP_WLDS WaveArgs& a = *(const DNLP_WLDS WaveArgs*)g_wg_args;
+  using P = WaveLanesWG;
+  using W = WaveIpm<P>;
+  const int wave = static_cast<int>(threadIdx.x >> 6), tid = static_cast<int>(threadIdx.x);
+  WGlbD* base = (WGlbD*)(a.state + static_cast<size_t>(blockIdx.x) * static_cast<size_t>(wspec::kStateDoubles));
+  if (tid == 0) { g_wg_vbase = base; g_wg_plan = (WGlbI*)a.blk; g_wg_gen = (DNLP_WGLB const unsigned*)a.gen; }
+  if ((tid & 63) == 0) g_wg_turn[wave] = 0u;
+  __syncthreads();
+  typename W::WS* S = (typename W::WS*)g_wg_rec[wave].rec;
+  while (true) {
+    if (tid == 0) g_wg_inst = atomicAdd(a.next, 1);
+    __syncthreads();
+    const int inst = g_wg_inst;
+    __syncthreads();
+    if (inst >= a.batch) break;
+    for (int k = tid; k < wspec::kStateDoubles; k += P::lanes) base[k] = 0.0;
+    for (int k = tid; k < wspec::kLdsDoubles; k += P::lanes) g_wg_lds[k] = 0.0;
+    S->row = (WG*)(a.rows + static_cast<i64>(inst) * a.row_doubles);
+    S->park = a.park + static_cast<i64>(blockIdx.x) * a.park_doubles;
+    S->ws_g = S->ws_l = S->ws_u = nullptr;
+    S->fallback_max_n = a.fallback_max_n;
+    S->opt = a.opt;
+#ifdef DNLP_WAVE_PROF
+    for (int k = 0; k < kWaveProfSlots; ++k) S->prof[k] = 0ull;
+#endif
+    __syncthreads();
+    W::probe(S, a.probe, inst);
+    __syncthreads();
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(wspec::kWgBound) dnlp_wave_wg_probe_kernel(dnlp::WaveArgs a) {
+  for (unsigned k = threadIdx.x; k < sizeof(dnlp::WaveArgs) / 4; k += blockDim.x) g_wg_args[k] = ((const unsigned*)&a)[k];
+  __syncthreads();
+  dnlp_wave_wg_probe_main();
+}

@@ -349,10 +349,35 @@ int dnlp_ldlt_device(int device, double* device_A, int64_t n, int64_t ld, int* n
  * A probe leaves nothing behind that changes a later solve — except the demotions of the KKT object, which are the
  * handle's real state and are not hidden: a dense tail or a paired factorisation that met a zero pivot or excessive
  * growth hands itself to Bunch-Kaufman for good, also when a probe's matrix caused it (tests: one handle per case).
- * Host-driven handles only; the batch kernels have no such entry. */
+ * Host-driven handles only; the batch kernels' entry is dnlp_batch_kkt_probe. */
 int dnlp_kkt_probe(dnlp_problem* p, const double* x, const double* lambda, double obj_factor, const double* Sx,
                    const double* D, const double* fixmask, double delta_w, int nrhs, const double* rhs, double* sol,
                    int* nneg, int* nzero);
+/* The same for the WAVEFRONT BATCH SOLVER (the kernels a dnlp_solve_batch launch of `batch` instances would run: the
+ * library's own forms, the per-template kernel or the workgroup-per-instance kernel, chosen as that launch chooses, by
+ * the launch size and the same environment switches; dnlp_batch_launch_info afterwards describes the launch).  data:
+ * batch x stride instance rows as for dnlp_solve_batch.  Per instance, the kernel's own restatement of the linear
+ * algebra runs ONCE on
+ *     K = [[H + diag(Sx) + delta_w I, J^T], [J, -diag(D)]]
+ * at the given point x (batch x N) and multipliers lambda (batch x m) with Sx (batch x N) and D (batch x m): bounds,
+ * the equality mask and the fixed variables (lb == ub in the instance's row: the row and column of the identity) come
+ * from the row as a solve takes them — but NO scaling (objective and constraints as written), NO bound relaxation, NO
+ * push of the point into its bounds, NO iterative refinement, NO inertia loop, NO retry.
+ *   sol   batch x nrhs x (N + m)   one plain solve per right-hand side (rhs: batch x nrhs x (N + m))
+ *   sol2  batch x 2 x (N + m)      right-hand sides 0 and 1 solved jointly (the mu oracle's two-system solve); nrhs >= 2
+ *   res   batch x 3 x (N + m)      the kernel's one-pass residual: rhs 0 - K v 0 alone, then (rhs 0 - K v 0, rhs 1 - K v 1)
+ *                                  by the two-system pass (nrhs >= 2); v: batch x nv x (N + m), nv = 2 when nrhs >= 2 else 1;
+ *                                  v may be NULL (no residual; res is untouched).  The pass is the solver's own: it multiplies
+ *                                  by the WHOLE Hessian and Jacobian and takes the identity only in the rows of fixed
+ *                                  variables, so it is rhs - K v for vectors whose FIXED COMPONENTS ARE ZERO (what a solve
+ *                                  hands it: a right-hand side's fixed components are zero); other v are the caller's error
+ *   nneg, nzero, ok   batch        the factorisation's inertia counts and 1 when it met no NaN
+ * Returns 0; -2 when the wavefront solver does not take this template or launch (dnlp_last_error says why: no result of
+ * the generic kernel stands in); -199 on misuse.  The host library runs the same text on one host lane. */
+int dnlp_batch_kkt_probe(dnlp_problem* p, int batch, const double* data, int64_t stride, const double* x,
+                         const double* lambda, const double* Sx, const double* D, double delta_w, int nrhs,
+                         const double* rhs, const double* v, double* sol, double* sol2, double* res, int* nneg, int* nzero,
+                         int* ok);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,150 @@ extern "C" int orc_wave_solve_batch(orc_problem* vp, int batch, const double* da
     return 0;)
 }
 
+// The factorisation measured on its own (include/dnlp_hip.h dnlp_batch_kkt_probe; wave_ipm.h WaveIpm::probe), instance by
+// instance.  which = 0: wave_ipm.h on one host lane; which = 1: the generic text (Model / DenseKkt / Ipm over HostExec)
+// with the template's plan, set up as orc_wave_solve_batch sets it up, doing what the probe does — no scaling, the
+// given point and multipliers, the evaluation calls of a solve, ONE assemble_factor, plain solves, kkt_residual (the
+// generic text has neither a joint solve nor a two-system residual: each system on its own fills those outputs).
+// Arguments as dnlp_batch_kkt_probe.  -2: the wavefront solver refuses the template (orc_last_error says why).
+extern "C" int orc_wave_probe(orc_problem* vp, int batch, const double* data, int64_t stride, int which, const double* x, const double* lambda,
+                              const double* Sx, const double* D, double delta_w, int nrhs, const double* rhs, const double* v, double* sol,
+                              double* sol2, double* res, int* nneg, int* nzero, int* ok) {
+  using namespace dnlp;
+  orc_problem_t* p = vp;
+  DNLP_TRY(
+    if (!p) throw std::runtime_error("orc_wave_probe: null handle");
+    p->plan_linear_solver();
+    const Tape<HostExec>& t = *p->model.owner;
+    if (batch < 0 || nrhs < 0 || (batch > 0 && (!data || !x || !Sx || (t.m > 0 && (!lambda || !D)) || !nneg || !nzero || !ok ||
+                                                (nrhs > 0 && (!rhs || !sol)) || (nrhs >= 2 && !sol2) || (v && (!res || nrhs < 1)))))
+      throw std::runtime_error("orc_wave_probe: a required argument is null, or batch or nrhs is negative, or v is given without a right-hand side");
+    if (!p->use_sparse) { tls_error() = "orc_wave_probe: the wavefront solver does not take this launch: no sparse plan for this tape"; return -2; }
+    const char* why = wave_plan_refusal(t, &p->sparse_plan);
+    if (why[0]) { tls_error() = std::string("orc_wave_probe: the wavefront solver does not take this launch: ") + why; return -2; }
+    const WaveLayoutIn lay = wave_layout_of(t);
+    const i64 head = 1 + (t.N + t.Z) + t.m + t.nnzJ + t.G.nnz + t.Mg.nnz + t.Mw.nnz + t.MJ.nnz + t.MH.nnz;
+    const i64 tail = 3 * t.N + 2 * t.m;
+    if (stride != head + 2 * t.nseg + tail) throw std::runtime_error("orc_wave_probe: instance stride does not match the tape");
+    const i64 N = t.N, m = t.m, n = N + m;
+    std::vector<double> row(static_cast<size_t>(lay.total));
+    std::vector<i32> blk;
+    std::vector<double> state;
+    if (which == 0) {
+      blk = build_wave_plan(&p->ex, t, p->sparse_plan, lay);
+      state.assign(static_cast<size_t>(reinterpret_cast<const WaveHdr*>(blk.data())->state_doubles) + 8, 0.0);
+    }
+    WaveProbe io;
+    io.x = x; io.lam = lambda; io.Sx = Sx; io.D = D; io.rhs = rhs; io.v = v; io.dw = delta_w; io.nrhs = nrhs;
+    io.sol = sol; io.sol2 = sol2; io.res = res; io.nneg = nneg; io.nzero = nzero; io.ok = ok;
+    const int nv = nrhs >= 2 ? 2 : 1;
+    for (int k = 0; k < batch; ++k) {
+      const double* src = data + static_cast<i64>(k) * stride;
+      std::copy(src, src + head, row.begin());
+      const double *sp = src + head, *sp2 = sp + t.nseg;
+      for (i64 f = 0; f < t.nflat; ++f) {
+        row[static_cast<size_t>(lay.fp + f)] = sp[t.h_flat_seg[static_cast<size_t>(f)]];
+        row[static_cast<size_t>(lay.fp2 + f)] = sp2[t.h_flat_seg[static_cast<size_t>(f)]];
+      }
+      std::copy(sp2 + t.nseg, sp2 + t.nseg + tail, row.begin() + lay.x0);
+      if (which == 0) {
+        WaveIpm<HostLane>::WState S;
+        std::fill(state.begin(), state.end(), 0.0);
+        if (WaveIpm<HostLane>::layout(&S, reinterpret_cast<const WaveHdr*>(blk.data()), blk.data(), state.data()) !=
+            reinterpret_cast<const WaveHdr*>(blk.data())->state_doubles) throw std::runtime_error("wave layout and wave_state_doubles disagree");
+        S.row = row.data();
+        S.park = nullptr;
+        S.ws_g = S.ws_l = S.ws_u = nullptr;
+        S.fallback_max_n = 0;
+        S.opt = p->opt;
+        WaveIpm<HostLane>::probe(&S, &io, k);
+      } else {
+        HostExec ex;
+        TapeView tv = t;
+        tv.c0 = row[static_cast<size_t>(lay.c0)];
+        tv.c = row.data() + lay.c; tv.b = row.data() + lay.b; tv.Jc = row.data() + lay.Jc;
+        tv.G.val = row.data() + lay.G; tv.Mg.val = row.data() + lay.Mg; tv.Mw.val = row.data() + lay.Mw; tv.MJ.val = row.data() + lay.MJ;
+        tv.MH.val = row.data() + lay.MH;
+        tv.flat_p = row.data() + lay.fp; tv.flat_p2 = row.data() + lay.fp2;
+        tv.d_x0 = row.data() + lay.x0; tv.d_lb = row.data() + lay.lb; tv.d_ub = row.data() + lay.ub; tv.d_cl = row.data() + lay.cl; tv.d_cu = row.data() + lay.cu;
+        Model<HostExec> md;
+        md.init_view(&ex, tv);
+        DenseKkt<HostExec> kkt;
+        SparsePlan pl = p->sparse_plan.upload(&ex);
+        kkt.init_sparse(&ex, tv.N, tv.m, pl);
+        kkt.pivot_max_n = static_cast<i64>(1) << 40;
+        kkt.fallback_max_n = 0;
+        Ipm<HostExec, DenseKkt<HostExec>> ipm(&ex, &md, &kkt);
+        ipm.opt = p->opt;
+        ipm.allocate();
+        const double inf = p->opt.nlp_inf;
+        double *ix = ipm.x, *iy = ipm.y, *isx = ipm.Sx, *idd = ipm.Dd, *ifm = ipm.fixmask, *isg = ipm.sg;
+        i64 nfix = 0;
+        for (i64 j = 0; j < N; ++j) {
+          const double a = tv.d_lb[j], b = tv.d_ub[j];
+          const double lj = a <= -inf ? -kInf : a, uj = b >= inf ? kInf : b;
+          ifm[j] = lj == uj ? 1.0 : 0.0;
+          nfix += lj == uj;
+          ix[j] = x[static_cast<i64>(k) * N + j];
+          isx[j] = Sx[static_cast<i64>(k) * N + j];
+        }
+        for (i64 i = 0; i < m; ++i) { isg[i] = 1.0; iy[i] = lambda[static_cast<i64>(k) * m + i]; idd[i] = D[static_cast<i64>(k) * m + i]; }
+        ipm.sf = 1.0;
+        kkt.n_fixed = nfix;
+        double fv = 0.0;
+        (void)ipm.eval_fg(ipm.x, fv, ipm.g, false);
+        ipm.eval_derivs_after_sweep();
+        ipm.eval_hessian();
+        int ng = 0, nz = 0;
+        const bool okf = kkt.assemble_factor(md, ipm.jv, ipm.Sx, ipm.Dd, ipm.fixmask, delta_w, &ng, &nz);
+        nneg[k] = ng; nzero[k] = nz; ok[k] = okf ? 1 : 0;
+        double *r1 = ipm.rhs, *s1 = ipm.sol, *e1 = ipm.res;
+        const double* R = rhs + static_cast<i64>(k) * nrhs * n;
+        for (int q = 0; q < nrhs; ++q) {
+          std::copy(R + static_cast<i64>(q) * n, R + static_cast<i64>(q + 1) * n, r1);
+          ipm.kkt_solve(r1, s1);
+          std::copy(s1, s1 + n, sol + (static_cast<i64>(k) * nrhs + q) * n);
+          if (nrhs >= 2 && q < 2) std::copy(s1, s1 + n, sol2 + (static_cast<i64>(k) * 2 + q) * n);
+        }
+        if (v && nrhs >= 1) {
+          const double* V = v + static_cast<i64>(k) * nv * n;
+          double* o = res + static_cast<i64>(k) * 3 * n;
+          for (int q = 0; q < nv; ++q) {
+            std::copy(R + static_cast<i64>(q) * n, R + static_cast<i64>(q + 1) * n, r1);
+            std::copy(V + static_cast<i64>(q) * n, V + static_cast<i64>(q + 1) * n, s1);
+            (void)ipm.kkt_residual(s1, delta_w, r1, e1);
+            if (q == 0) std::copy(e1, e1 + n, o);
+            if (nrhs >= 2) std::copy(e1, e1 + n, o + static_cast<i64>(q + 1) * n);
+          }
+        }
+      }
+    }
+    return 0;)
+}
+// the host library's export of the C ABI entry (include/dnlp_hip.h dnlp_batch_kkt_probe): the same text on one host lane
+extern "C" int orc_batch_kkt_probe(orc_problem* vp, int batch, const double* data, int64_t stride, const double* x, const double* lambda,
+                                   const double* Sx, const double* D, double delta_w, int nrhs, const double* rhs, const double* v, double* sol,
+                                   double* sol2, double* res, int* nneg, int* nzero, int* ok) {
+  return orc_wave_probe(vp, batch, data, stride, 0, x, lambda, Sx, D, delta_w, nrhs, rhs, v, sol, sol2, res, nneg, nzero, ok);
+}
+// the header of the plan block the wavefront solver builds for this template, as 32-bit words (wave_hdr.h WaveHdr, in
+// declaration order); returns their number, -2 when the template is refused.  no_tail != 0: without the dense tail in
+// registers (the workgroup-per-instance kernel's block).
+extern "C" int orc_wave_hdr(orc_problem* vp, int no_tail, int32_t* out, int cap) {
+  using namespace dnlp;
+  orc_problem_t* p = vp;
+  DNLP_TRY(
+    p->plan_linear_solver();
+    const Tape<HostExec>& t = *p->model.owner;
+    if (!p->use_sparse) { tls_error() = "no sparse plan for this tape"; return -2; }
+    const char* why = wave_plan_refusal(t, &p->sparse_plan);
+    if (why[0]) { tls_error() = why; return -2; }
+    const std::vector<i32> blk = build_wave_plan(&p->ex, t, p->sparse_plan, wave_layout_of(t), no_tail == 0);
+    const int nw = static_cast<int>(sizeof(WaveHdr) / 4);
+    for (int k = 0; k < nw && k < cap; ++k) out[k] = blk[static_cast<size_t>(k)];
+    return nw;)
+}
+
 // The text of a template's per-template kernel (dnlp_amd/csrc/wave_codegen.h), as the product library would hand it to
 // hiprtc: tests compile it for gfx950 without a GPU.  Returns the length of the text (0-terminated copy in buf when it fits),
 // a negative code when the template is not the wavefront solver's.
@@ -320,6 +464,32 @@ extern "C" int wgen_host_solve(int batch, const double* rows, long long row_doub
       zu[static_cast<long long>(k) * wspec::k_N + j] = b[j] / S->sf;
     }
     for (int i = 0; i < wspec::k_m; ++i) mult_g[static_cast<long long>(k) * wspec::k_m + i] = yy[i] * sg[i] / S->sf;
+  }
+  return 0;
+}
+// the probe of the same unit (wave_ipm.h WaveIpm::probe; arguments as dnlp_batch_kkt_probe behind the expanded rows)
+extern "C" int wgen_host_probe(int batch, const double* rows, long long row_doubles, const void* opt_bytes, long long opt_size, const double* x,
+                               const double* lam, const double* Sx, const double* D, double dw, int nrhs, const double* rhs, const double* v,
+                               double* sol, double* sol2, double* res, int* nneg, int* nzero, int* ok) {
+  using namespace dnlp;
+  typedef HostSpecLane P;
+  typedef WaveIpm<P> W;
+  if (opt_size != static_cast<long long>(sizeof(IpmOptions))) return -1;
+  std::vector<double> state(static_cast<size_t>(wspec::kStateDoubles) + 64, 0.0);
+  g_vec = state.data();
+  WaveProbe io;
+  io.x = x; io.lam = lam; io.Sx = Sx; io.D = D; io.rhs = rhs; io.v = v; io.dw = dw; io.nrhs = nrhs;
+  io.sol = sol; io.sol2 = sol2; io.res = res; io.nneg = nneg; io.nzero = nzero; io.ok = ok;
+  for (int k = 0; k < batch; ++k) {
+    W::WState st;
+    W::WState* S = &st;
+    std::fill(state.begin(), state.end(), 0.0);
+    S->row = rows + static_cast<long long>(k) * row_doubles;
+    S->park = nullptr;
+    S->ws_g = S->ws_l = S->ws_u = nullptr;
+    S->fallback_max_n = 0;
+    std::memcpy(&S->opt, opt_bytes, sizeof(IpmOptions));
+    W::probe(S, &io, k);
   }
   return 0;
 }

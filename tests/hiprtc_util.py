@@ -39,8 +39,8 @@ def compile_for_gfx950(src: str, opts=("-O3", "-std=c++17", "-munsafe-fp-atomics
     return rc == 0, log.value.decode(errors="replace"), dt, code
 
 
-def registers_of(code: bytes):
-    """-> (vgpr_count, agpr_count, max_flat_workgroup_size) of the first kernel in a code object (its metadata note)."""
+def kernels_of(code: bytes):
+    """-> {kernel name: (vgpr_count, agpr_count, max_flat_workgroup_size)} of a code object (its metadata note), in its order."""
     import os
     import re
     import subprocess
@@ -51,12 +51,21 @@ def registers_of(code: bytes):
         out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
     finally:
         os.unlink(f.name)
-    g = lambda key: int(re.search(r"\.%s:\s*(\d+)" % key, out).group(1))
-    return g("vgpr_count"), g("agpr_count"), g("max_flat_workgroup_size")
+    found = {}
+    for part in re.split(r"\n\s*- \.agpr_count:", out)[1:]:       # (the keys of a kernel's map are sorted: .agpr_count comes first)
+        part = ".agpr_count:" + part
+        g = lambda key: int(re.search(r"\.%s:\s*(\d+)" % key, part).group(1))
+        found[re.search(r"\.name:\s*(\S+)", part).group(1)] = (g("vgpr_count"), g("agpr_count"), g("max_flat_workgroup_size"))
+    return found
+
+
+def registers_of(code: bytes, name=None):
+    """-> (vgpr_count, agpr_count, max_flat_workgroup_size) of the kernel `name` of a code object (default: its first kernel)."""
+    found = kernels_of(code)
+    return found[name] if name else next(iter(found.values()))
 
 
 def fits_register_file(code: bytes, waves: int) -> bool:
     """gfx950: 512 unified registers per lane and SIMD, four SIMDs per compute unit — ceil(waves / 4) wavefronts of a workgroup
-    share one (the rule of csrc/fused_rtc.h RtcKernel::fits)."""
-    v, a, bound = registers_of(code)
-    return v * ((waves + 3) // 4) <= 512
+    share one (the rule of csrc/fused_rtc.h RtcKernel::fits).  Every kernel of the code object has to fit."""
+    return all(v * ((waves + 3) // 4) <= 512 for v, a, bound in kernels_of(code).values())

@@ -78,6 +78,32 @@ class GenHostBatch(HostBatch):
             raise RuntimeError("wgen_host_solve: %d" % rc)
         return out
 
+    def probe_gen(self, inp):
+        """WaveIpm::probe of the same unit (`wgen_host_probe`); `inp`: wave_probe_problems.inputs.  Returns what
+        wave_probe_problems.host_probe returns."""
+        mat = np.ascontiguousarray(inp["data"])
+        B, nrhs, n = inp["rhs"].shape
+        opt = C.create_string_buffer(1024)
+        fb = C.c_int(0)
+        width = self._expand(self.handle.ptr, B, mat.ctypes.data_as(_dp), mat.shape[1], None, opt, len(opt), C.byref(fb))
+        assert width > 0, self.lib.orc_last_error()
+        rows = np.zeros((B, width))
+        rc = self._expand(self.handle.ptr, B, mat.ctypes.data_as(_dp), mat.shape[1], rows.ctypes.data_as(_dp), opt, len(opt), C.byref(fb))
+        assert rc == width, (rc, self.lib.orc_last_error())
+        f = self.gen.wgen_host_probe
+        f.restype = C.c_int
+        f.argtypes = [C.c_int, _dp, C.c_longlong, C.c_void_p, C.c_longlong] + [_dp] * 4 + [C.c_double, C.c_int] + [_dp] * 5 + [_ip] * 3
+        keep = [np.ascontiguousarray(inp[k], dtype=np.float64) for k in ("x", "lagrange", "Sx", "D", "rhs", "v")]
+        sol, sol2, res = np.full((B, nrhs, n), np.nan), np.full((B, 2, n), np.nan), np.full((B, 3, n), np.nan)
+        nneg, nzero, ok = (np.zeros(B, np.int32) for _ in range(3))
+        rc = f(B, rows.ctypes.data_as(_dp), width, opt, self._opt_size(), keep[0].ctypes.data_as(_dp), keep[1].ctypes.data_as(_dp),
+               keep[2].ctypes.data_as(_dp), keep[3].ctypes.data_as(_dp), float(inp["delta_w"]), nrhs, keep[4].ctypes.data_as(_dp),
+               keep[5].ctypes.data_as(_dp), sol.ctypes.data_as(_dp), sol2.ctypes.data_as(_dp), res.ctypes.data_as(_dp),
+               nneg.ctypes.data_as(_ip), nzero.ctypes.data_as(_ip), ok.ctypes.data_as(_ip))
+        if rc != 0:
+            raise RuntimeError("wgen_host_probe: %d" % rc)
+        return {"sol": sol, "sol2": sol2, "res": res, "nneg": nneg, "nzero": nzero, "ok": ok.astype(bool)}
+
     def _opt_size(self):
         f = self.lib.orc_sizeof_ipm_options
         f.restype = C.c_longlong
