@@ -14,7 +14,9 @@
 //                              owns 64 x 32 (2 x 4 MFMA tiles, 64 accumulator VGPRs, four wavefronts per SIMD,
 //                              two workgroups per CU), operand k-tiles go global -> LDS directly
 //                              (global_load_lds_dwordx4), double buffered, one barrier per 16-deep k-tile,
-//                              LDS rows padded by 16 doubles.  Edge tiles, unaligned operands and K not a
+//                              LDS rows padded by 16 doubles.  Default form (gemm_nt_update_fast_v): operand
+//                              reads software pipelined over two register sets, and `lower` launches start only
+//                              the tiles of the lower triangle (lower_tile_map.h).  Edge tiles, unaligned operands and K not a
 //                              multiple of 16 take gemm_nt_update: four wavefronts of 64 x 64, operands staged
 //                              through registers.
 //   The MFMA computes D[row=j][col=i] so that lane&15 walks the contiguous (row) direction
@@ -24,6 +26,7 @@
 // caller's regularisation loop (WB Algorithm IC) can react.
 #pragma once
 #include "exec_hip.h"
+#include "lower_tile_map.h"
 
 namespace dnlp {
 
@@ -683,7 +686,13 @@ __device__ inline void gemm_body_guarded(double* __restrict__ C, i64 ldc, const 
 // MASKED = tile on the diagonal or on the last (partial) tile row / column: C accesses are
 // predicated; operand rows past M / Nc are read from the (padded) allocations and only feed
 // accumulators that are never stored.
-template <bool MASKED>
+//
+// PIPE = 1: the operand reads are software pipelined.  Two register sets; the ds_reads of k-group g + 1 are issued
+// ahead of the eight MFMAs of group g, so a wave waits (counted lgkmcnt) only for reads that have had a whole MFMA group
+// to land; the first group of the NEXT k-tile is read right behind the barrier, ahead of the last group's MFMAs; and
+// the LDS-DMA of the next-but-one tile is issued behind the first MFMA group, off the barrier -> first-MFMA path.  Each
+// accumulator still takes the same products in the same k order: the result is bit for bit that of PIPE = 0.
+template <bool MASKED, int PIPE = 0>
 __device__ inline void gemm_body_fast(double* __restrict__ C, i64 ldc, const double* __restrict__ W, i64 ldw,
                                       const double* __restrict__ L, i64 ldl, int Kd, int tm, int tn, double* smem,
                                       int M, int Nc, int lower) {
@@ -729,34 +738,96 @@ __device__ inline void gemm_body_fast(double* __restrict__ C, i64 ldc, const dou
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
-    const double* ws = smem + (kt & 1) * 2 * TILE;
-    const double* ls = ws + TILE;
-    if (kt + 1 < nkt) {
-      double* wd = smem + ((kt + 1) & 1) * 2 * TILE;
-      double* ldst = wd + TILE;
-      const i64 ko = static_cast<i64>(kt + 1) * GM_BK;
-      DNLP_GLDS(pw + ko * ldw, wd + wave * LDT);
-      DNLP_GLDS(pw + (ko + 8) * ldw, wd + (wave + 8) * LDT);
-      DNLP_GLDS(pl + ko * ldl, ldst + wave * LDT);
-      DNLP_GLDS(pl + (ko + 8) * ldl, ldst + (wave + 8) * LDT);
+  if constexpr (PIPE) {
+    const double* lrd = smem + TILE + (lane >> 4) * LDT + wn * 32 + (lane & 15);   // this lane's L (a) operand, k-group 0
+    const double* wrd = smem + (lane >> 4) * LDT + wm * 64 + (lane & 15);          // ... and W (b) operand
+    double a[2][2], b[2][4];
+#define DNLP_UPD_READ(set, buf, kk)                                                               \
+    {                                                                                             \
+      _Pragma("unroll") for (int t = 0; t < 2; ++t) a[set][t] = lrd[(buf) * 2 * TILE + (kk) * LDT + t * 16]; \
+      _Pragma("unroll") for (int t = 0; t < 4; ++t) b[set][t] = wrd[(buf) * 2 * TILE + (kk) * LDT + t * 16]; \
     }
+    DNLP_UPD_READ(0, 0, 0);
+    // one k-tile; LAST = no tile behind it to fetch (peeled, so that the loop body is one basic block and the
+    // compiler's counted waits see every read in issue order)
+    auto ktile = [&](int kt, auto last) {
+      const int cur = kt & 1, nxt = cur ^ 1;
 #pragma unroll
-    for (int kk = 0; kk < GM_BK; kk += 4) {
-      double a[2], b[4];
-      const int kr = kk + (lane >> 4), lc = lane & 15;
+      for (int g = 0; g < 4; ++g) {
+        // While an LDS-DMA is in flight the compiler turns every wait for a ds_read into lgkmcnt(0) (it counts the
+        // DMA as a pending LDS access).  Groups 1 and 2 wait under those terms, so their successors are read behind
+        // their first MFMA: the forced drain then falls where only reads issued seven MFMAs earlier are in flight.
+        constexpr bool kLastTile = decltype(last)::value;
+        const bool late = !kLastTile && (g == 1 || g == 2);
+        if (late) {
+        } else if (g < 3) {
+          DNLP_UPD_READ((g + 1) & 1, cur, 4 * (g + 1));
+        } else {
+          // every read of this k-tile has landed (the buffer may be overwritten behind the barrier) and the next
+          // tile's DMA is complete; behind the last k-tile the read below fetches stale LDS that nothing uses
+          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+          __syncthreads();
+          DNLP_UPD_READ(0, nxt, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int t = 0; t < 2; ++t) a[t] = ls[kr * LDT + wn * 32 + t * 16 + lc];
+        for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-      for (int t = 0; t < 4; ++t) b[t] = ws[kr * LDT + wm * 64 + t * 16 + lc];
+          for (int mi = 0; mi < 4; ++mi) {
+            acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[g & 1][ni], b[g & 1][mi], acc[ni][mi], 0, 0, 0);
+            if (late && ni == 0 && mi == 0) {
+              __builtin_amdgcn_sched_barrier(0);
+              DNLP_UPD_READ((g + 1) & 1, cur, 4 * (g + 1));
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!kLastTile) {
+          if (g == 0) {
+            double* wd = smem + nxt * 2 * TILE;
+            double* ldst = wd + TILE;
+            const i64 ko = static_cast<i64>(kt + 1) * GM_BK;
+            DNLP_GLDS(pw + ko * ldw, wd + wave * LDT);
+            DNLP_GLDS(pw + (ko + 8) * ldw, wd + (wave + 8) * LDT);
+            DNLP_GLDS(pl + ko * ldl, ldst + wave * LDT);
+            DNLP_GLDS(pl + (ko + 8) * ldl, ldst + (wave + 8) * LDT);
+          }
+        }
+      }
+    };
+    for (int kt = 0; kt + 1 < nkt; ++kt) ktile(kt, std::false_type{});
+    ktile(nkt - 1, std::true_type{});
+#undef DNLP_UPD_READ
+  } else {
+    for (int kt = 0; kt < nkt; ++kt) {
+      const double* ws = smem + (kt & 1) * 2 * TILE;
+      const double* ls = ws + TILE;
+      if (kt + 1 < nkt) {
+        double* wd = smem + ((kt + 1) & 1) * 2 * TILE;
+        double* ldst = wd + TILE;
+        const i64 ko = static_cast<i64>(kt + 1) * GM_BK;
+        DNLP_GLDS(pw + ko * ldw, wd + wave * LDT);
+        DNLP_GLDS(pw + (ko + 8) * ldw, wd + (wave + 8) * LDT);
+        DNLP_GLDS(pl + ko * ldl, ldst + wave * LDT);
+        DNLP_GLDS(pl + (ko + 8) * ldl, ldst + (wave + 8) * LDT);
+      }
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
+      for (int kk = 0; kk < GM_BK; kk += 4) {
+        double a[2], b[4];
+        const int kr = kk + (lane >> 4), lc = lane & 15;
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-          acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ni], b[mi], acc[ni][mi], 0, 0, 0);
+        for (int t = 0; t < 2; ++t) a[t] = ls[kr * LDT + wn * 32 + t * 16 + lc];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) b[t] = ws[kr * LDT + wm * 64 + t * 16 + lc];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi)
+            acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ni], b[mi], acc[ni][mi], 0, 0, 0);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
   }
   {
     double* cp = cbase;
@@ -812,6 +883,29 @@ __global__ void __launch_bounds__(512, 4) gemm_nt_update_fast(double* __restrict
     gemm_body_fast<false>(C, ldc, W, ldw, L, ldl, Kd, tm, tn, smem, M, Nc, lower);
   else
     gemm_body_fast<true>(C, ldc, W, ldw, L, ldl, Kd, tm, tn, smem, M, Nc, lower);
+}
+
+// The same tiles with the pipelined body (PIPE) and, with `vec_ok & 4`, a grid of the lower tiles only (`lower` with
+// Nc <= M, diagonal at the block origin): blockIdx.x counts them column by column (csrc/lower_tile_map.h), so no
+// workgroup is launched to find out that it has nothing to do.  DNLP_LDLT_UPDATE_FORM selects (BlockedLdlt::init).
+template <int PIPE>
+__global__ void __launch_bounds__(512, 4) gemm_nt_update_fast_v(double* __restrict__ C, i64 ldc,
+                                                                const double* __restrict__ W, i64 ldw,
+                                                                const double* __restrict__ L, i64 ldl, int M,
+                                                                int Nc, int Kd, int lower, int ntm, int ntn, int vec_ok) {
+  int tm, tn;
+  if (vec_ok & 4) {
+    lower_tile_map(blockIdx.x, ntm, ntn, &tm, &tn);
+  } else {
+    tm = blockIdx.x % ntm;
+    tn = blockIdx.x / ntm;
+    if (lower && (tm * GM_BM + GM_BM - 1 < tn * GM_BN)) return;
+  }
+  __shared__ __attribute__((aligned(16))) double smem[4 * GM_BK * (GM_BM + GM_PAD)];
+  if (gemm_tile_interior(tm, tn, M, Nc, Kd, lower, vec_ok & 1, C, ldc))
+    gemm_body_fast<false, PIPE>(C, ldc, W, ldw, L, ldl, Kd, tm, tn, smem, M, Nc, lower);
+  else
+    gemm_body_fast<true, PIPE>(C, ldc, W, ldw, L, ldl, Kd, tm, tn, smem, M, Nc, lower);
 }
 
 // every tile through the guarded path (unaligned operands or K not a multiple of 16)
@@ -1744,6 +1838,10 @@ struct BlockedLdlt {
   bool lookahead = true;
   bool xcd_swizzle = false;    // 8 x 8 super-tiles per XCD: cuts the W-strip re-reads ~5x but measured 1.5-3% slower (MFMA-bound), so off; DNLP_LDLT_XCD=1 enables
   bool padded = false;         // the matrix allocation has >= 128 doubles of slack behind it
+  // Schur update kernel (DNLP_LDLT_UPDATE_FORM): bit 0 = software-pipelined operand reads (gemm_body_fast<.., 1>),
+  // bit 1 = `lower` launches start only the tiles of the lower triangle; 0 = the single-register-set loop on the full
+  // ntm x ntn grid.  Every form gives the same bits.
+  int update_form = 3;
   int NB = 512;                // outer panel width (K of the MFMA Schur update)
   int small_tiles_below = 384; // launches with fewer 128 x 128 tiles than this use the 64 x 64 kernel (DNLP_LDLT_SMALL_TILES)
   int small_rows_max = 5120;   // ... and only up to this many rows: above, the launch runs beside a big update of the
@@ -1778,6 +1876,7 @@ struct BlockedLdlt {
     if (const char* ev = std::getenv("DNLP_LDLT_NB")) NB = std::atoi(ev);
     if (const char* ev = std::getenv("DNLP_LDLT_LOOKAHEAD")) lookahead = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("DNLP_LDLT_XCD")) xcd_swizzle = std::atoi(ev) != 0;
+    if (const char* ev = std::getenv("DNLP_LDLT_UPDATE_FORM")) update_form = std::atoi(ev) & 3;
     if (const char* ev = std::getenv("DNLP_LDLT_T128")) sub128 = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("DNLP_LDLT_FUSED_ROWS")) fused_rows = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("DNLP_LDLT_DIAG512")) diag512 = std::atoi(ev) != 0;
@@ -1854,6 +1953,15 @@ struct BlockedLdlt {
       const unsigned nsuper = static_cast<unsigned>((ntm + 7) / 8) * static_cast<unsigned>((ntn + 7) / 8);
       hipLaunchKernelGGL(gemm_nt_update_fast, dim3(((nsuper + 7) / 8) * 8 * 64), dim3(512), 0, st, C, ld, W,
                          ldw, L, ldl, M, Nc, Kd, lower, ntm, vec_ok | 2);
+    } else if (fast_ok && update_form != 0) {
+      const bool tri = (update_form & 2) && lower && ntn <= ntm;
+      const unsigned grid = tri ? static_cast<unsigned>(lower_tile_count(ntm, ntn)) : static_cast<unsigned>(ntm) * ntn;
+      if (update_form & 1)
+        hipLaunchKernelGGL(gemm_nt_update_fast_v<1>, dim3(grid), dim3(512), 0, st, C, ld, W, ldw, L, ldl, M, Nc, Kd,
+                           lower, ntm, ntn, vec_ok | (tri ? 4 : 0));
+      else
+        hipLaunchKernelGGL(gemm_nt_update_fast_v<0>, dim3(grid), dim3(512), 0, st, C, ld, W, ldw, L, ldl, M, Nc, Kd,
+                           lower, ntm, ntn, vec_ok | (tri ? 4 : 0));
     } else if (fast_ok)
       hipLaunchKernelGGL(gemm_nt_update_fast, dim3(static_cast<unsigned>(ntm) * ntn), dim3(512), 0, st, C, ld, W,
                          ldw, L, ldl, M, Nc, Kd, lower, ntm, vec_ok);
