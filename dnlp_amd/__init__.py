@@ -17,7 +17,7 @@ from .error import DeviceUnavailableError, DNLPError, SolverError  # noqa: F401
 from .expressions import Constant, DeviceMatrix, Expression, Parameter, Variable  # noqa: F401
 from .atoms import (  # noqa: F401
     AddExpression, DivExpression, MatrixFrac, MulExpression, NegExpression, Pnorm, Prod, Promote, QuadForm, QuadOverLinRows, Sum,
-    abs, asinh, atanh, broadcast_to, cos, entr, exp, geo_mean, hstack, huber, index, kl_div,
+    abs, acos, asin, asinh, atan, atan2, atanh, broadcast_to, cos, cosh, entr, exp, geo_mean, hstack, huber, index, kl_div,
     log, log_det, log_normcdf, log_sum_exp, loggamma, logistic, matmul, matrix_frac, max, maximum, min, minimum, multiply, norm, norm1, norm2, norm_inf,
     normcdf,
     pnorm, power, prod, promote, quad_form, quad_over_lin, quad_over_lin_rows, rel_entr, reshape, sin, sinh,

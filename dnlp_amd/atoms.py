@@ -802,6 +802,98 @@ class atanh(_Unary):
             return np.arctanh(values[0])
 
 
+class cosh(_Unary):
+    """cosh x: convex, positive, increasing on a non-negative argument and decreasing on a non-positive one; smooth (ESR and
+    HSR).  The reference has sinh and tanh and no cosh; tape op 17 (csrc/atom_math.h cosh_rules)."""
+    CONVEX = True
+
+    def is_incr(self, idx):
+        return self.args[0].is_nonneg()
+
+    def is_decr(self, idx):
+        return self.args[0].is_nonpos()
+
+    def numeric(self, values):
+        with np.errstate(over="ignore"):
+            return np.cosh(values[0])
+
+    def sign_from_args(self):
+        return (True, False)
+
+
+class _OddIncreasing(_Unary):
+    """An odd, increasing atom: the sign of its argument; its curvature on a signed argument is the subclass's."""
+    INCR = True
+    CONCAVE_ON_NONNEG = False        # atan bends down right of the origin (and up left of it), asin the other way
+
+    def is_atom_convex(self):
+        return self.args[0].is_nonpos() if self.CONCAVE_ON_NONNEG else self.args[0].is_nonneg()
+
+    def is_atom_concave(self):
+        return self.args[0].is_nonneg() if self.CONCAVE_ON_NONNEG else self.args[0].is_nonpos()
+
+    def sign_from_args(self):
+        return (self.args[0].is_nonneg(), self.args[0].is_nonpos())
+
+
+class atan(_OddIncreasing):
+    """atan x: increasing, the sign of its argument, concave on a non-negative argument (convex on a non-positive one), no
+    domain; smooth.  The reference has no arctangent; tape op 18 (csrc/atom_math.h atan_rules)."""
+    CONCAVE_ON_NONNEG = True
+
+    def numeric(self, values):
+        return np.arctan(values[0])
+
+
+class asin(_OddIncreasing):
+    """asin x on [-1, 1]: increasing, the sign of its argument, convex on a non-negative argument (concave on a non-positive
+    one); smooth inside the domain.  Tape op 19 (csrc/atom_math.h asin_rules); `acos` is pi / 2 - asin."""
+
+    def numeric(self, values):
+        with np.errstate(invalid="ignore"):
+            return np.arcsin(values[0])
+
+    def point_in_domain(self):
+        return np.zeros(self.shape)
+
+
+def acos(x):
+    """acos x = pi / 2 - asin(x): no atom and no tape op of its own."""
+    return np.pi / 2 - asin(x)
+
+
+class atan2(Elementwise):
+    """atan2(y, x), the angle of the point (x, y) in (-pi, pi]: smooth away from the origin (ESR and HSR), sign unknown,
+    neither convex nor concave, monotone in neither argument.  The value jumps by 2 pi across the negative x axis while its
+    derivatives are continuous there: keep the lines of sight of a model away from that cut, or rotate the frame.  A scalar
+    argument is broadcast against an array as `multiply` does.  Tape op 22 (csrc/atom_math.h atan2_rules)."""
+
+    def __init__(self, y, x):
+        y, x = Expression.broadcast(y, x)
+        super().__init__(y, x)
+
+    def numeric(self, values):
+        return np.arctan2(np.asarray(values[0], float), np.asarray(values[1], float))
+
+    def sign_from_args(self):
+        return (False, False)
+
+    def is_atom_convex(self):
+        return False
+
+    def is_atom_concave(self):
+        return False
+
+    def is_incr(self, idx):
+        return False
+
+    def is_decr(self, idx):
+        return False
+
+    def point_in_domain(self, argument=0):
+        return np.ones(self.args[argument].shape)
+
+
 def _rational_power(p, max_denom=1024):
     """Rational approximation used by the reference for derivative exponents
     (reference power.py:152-178, utilities/power_tools.py:106-149)."""

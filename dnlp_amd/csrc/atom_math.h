@@ -11,7 +11,9 @@ enum Op : int {
   OP_EXP = 1, OP_LOG = 2, OP_ENTR = 3, OP_LOGISTIC = 4, OP_POWER = 5, OP_SIN = 6, OP_COS = 7,
   OP_TAN = 8, OP_SINH = 9, OP_TANH = 10, OP_ASINH = 11, OP_ATANH = 12, OP_XEXP = 13,
   OP_LOG_NORMCDF = 14, OP_NORMCDF = 15, OP_LOGGAMMA = 16,     // no reference rule: exact smooth atoms
+  OP_COSH = 17, OP_ATAN = 18, OP_ASIN = 19,                    // no reference rule either: the partners of sinh / tan / sin (acos = pi / 2 - asin)
   OP_MUL = 20, OP_REL_ENTR = 21,
+  OP_ATAN2 = 22,           // two arguments like OP_REL_ENTR: argument 0 is y, argument 1 is x
   OP_QUAD_FORM_DENSE = 30, OP_QUAD_FORM_SPARSE = 31, OP_QUAD_OVER_LIN = 32, OP_MATMUL = 33,
   OP_LOG_SUM_EXP = 34,     // row class (model.h sweep_rows): M rows of K entries, one dense K x K Hessian block per row
   OP_PROD = 35,            // row class: the same rows; the block's diagonal is zero and only the strict triangle is stored
@@ -165,6 +167,37 @@ DNLP_OUTLINE DNLP_HD inline Rule3 loggamma_rules(double u) {
   return {nan, nan, nan};
 }
 
+// ---- cosh, atan, asin and the four-quadrant atan2 (ops 17 - 19 and 22) ------------------------------------
+// Closed-form derivatives without a second transcendental.  Functions of their own on the device for the reason above.
+DNLP_OUTLINE DNLP_HD inline Rule3 cosh_rules(double u) {
+  const double ch = cosh(u);
+  return {ch, sinh(u), ch};
+}
+
+// d2 = -2 u / (1 + u^2)^2 as (-2 u d1) d1: (1 + u^2)^2 overflows from |u| = 1e77 on, where the true value is a normal number up
+// to 1e102.  |u| >= 1.4e154: 1 + u^2 = inf, d1 = 0 and d2 = -+0 (the true values lie below the subnormal range).
+DNLP_OUTLINE DNLP_HD inline Rule3 atan_rules(double u) {
+  const double d1 = 1.0 / (1.0 + u * u);
+  return {atan(u), d1, (-2.0 * u * d1) * d1};
+}
+
+// 1 - u^2 as (1 - u) (1 + u): 1 - u u cancels next to +-1, the two factors are exact there (1 - u) or rounded once (1 + u).
+// |u| = 1: s = 0, d1 = +inf, d2 = +-inf; |u| > 1: sqrt of a negative number, NaN throughout, like asin's own value.
+DNLP_OUTLINE DNLP_HD inline Rule3 asin_rules(double u) {
+  const double s = (1.0 - u) * (1.0 + u), rt = sqrt(s);
+  return {asin(u), 1.0 / rt, u / (s * rt)};
+}
+
+// atan2(y, x) with r^2 = x^2 + y^2: gy = x / r^2, gx = -y / r^2, hyy = -2 x y / r^4 = 2 gy gx, hxx = -hyy,
+// hyx = (y - x) (y + x) / r^4.  Every fourth power is a product of two quotients by r^2, so nothing leaves the double range that
+// r^2 itself does not.  The origin: value per IEEE atan2, derivatives 0 / 0 = NaN.  The value jumps by 2 pi across the negative
+// x axis; the derivatives are continuous there.
+struct Rule2x2 { double val, gy, gx, hyy, hyx; };
+DNLP_OUTLINE DNLP_HD inline Rule2x2 atan2_rules(double y, double x) {
+  const double r2 = x * x + y * y, gy = x / r2, gx = -y / r2;
+  return {atan2(y, x), gy, gx, 2.0 * gy * gx, ((y - x) / r2) * ((y + x) / r2)};
+}
+
 // value, d/du, d2/du2 of a unary atom.  p_der is the derivative exponent (reference uses
 // p_rational there, power.py:410-419,433-450), p_fwd the forward one (power.py:187-188).
 DNLP_HD inline void unary_rules(int op, double u, double p_der, double p_fwd, double& val,
@@ -210,6 +243,9 @@ DNLP_HD inline void unary_rules(int op, double u, double p_der, double p_fwd, do
     case OP_LOG_NORMCDF: { const Rule3 r = log_normcdf_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
     case OP_NORMCDF: { const Rule3 r = normcdf_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
     case OP_LOGGAMMA: { const Rule3 r = loggamma_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
+    case OP_COSH: { const Rule3 r = cosh_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
+    case OP_ATAN: { const Rule3 r = atan_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
+    case OP_ASIN: { const Rule3 r = asin_rules(u); val = r.val; d1 = r.d1; d2 = r.d2; break; }
     default: val = d1 = d2 = 0.0;
   }
 }

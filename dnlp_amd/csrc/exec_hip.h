@@ -781,6 +781,19 @@ __device__ inline void sweep_one_unit(const FlatTable& t, i64 s, i64 i, const do
       hv[t.hoff[s] + n + i] = wi * u / (v * v);
       hv[t.hoff[s] + 2 * n + i] = -wi / v;
     }
+  } else if (op == OP_ATAN2) {
+    const i64 yi = t.a0b[s] >= 0 ? t.a0b[s] + i : t.gidx[t.a0o[s] + i];
+    const i64 xi = t.a1b[s] >= 0 ? t.a1b[s] + i : t.gidx[t.a1o[s] + i];
+    const Rule2x2 r = atan2_rules(x[yi], x[xi]);
+    z[t.zoff[s] + i] = r.val;
+    dv[t.doff[s] + i] = r.gy;
+    dv[t.doff[s] + n + i] = r.gx;
+    if (with_h) {
+      const double wi = ww[t.zoff[s] + i];
+      hv[t.hoff[s] + i] = wi * r.hyy;
+      hv[t.hoff[s] + n + i] = -(wi * r.hyy);
+      hv[t.hoff[s] + 2 * n + i] = wi * r.hyx;
+    }
   } else {   // OP_MATMUL
     const i64 mm = t.d0[s], kk = t.d1[s];
     const i64 r = i % mm, cidx = i / mm;

@@ -144,6 +144,20 @@ struct Model {
           hv[hoff[s] + n + i] = wi * u / (v * v);
           hv[hoff[s] + 2 * n + i] = -wi / v;
         }
+      } else if (op == OP_ATAN2) {
+        // atom_math.h atan2_rules: argument 0 is y, argument 1 is x; runs (y, y), (x, x), (y, x) like rel_entr's
+        const i64 yi = a0b[s] >= 0 ? a0b[s] + i : gidx[a0o[s] + i];
+        const i64 xi = a1b[s] >= 0 ? a1b[s] + i : gidx[a1o[s] + i];
+        const Rule2x2 r = atan2_rules(x[yi], x[xi]);
+        z[zoff[s] + i] = r.val;
+        dv[doff[s] + i] = r.gy;
+        dv[doff[s] + n + i] = r.gx;
+        if (with_h) {
+          const double wi = ww[zoff[s] + i];
+          hv[hoff[s] + i] = wi * r.hyy;
+          hv[hoff[s] + n + i] = -(wi * r.hyy);
+          hv[hoff[s] + 2 * n + i] = wi * r.hyx;
+        }
       } else {  // OP_MATMUL: unit = output entry (r, c) of U(mm x kk) @ V(kk x pp), F-order
         const i64 mm = d0[s], kk = d1[s];
         const i64 r = i % mm, cidx = i / mm;

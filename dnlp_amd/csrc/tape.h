@@ -326,6 +326,11 @@ struct Tape : TapeView {
       if (op_is_row(g.op)) { h_row_segs.push_back(s); continue; }
       if (!flat && !(g.op >= 30 && g.op <= 32)) throw std::runtime_error("tape segment with an unknown opcode: " + std::to_string(g.op));
       if (!flat) { h_red_segs.push_back(s); continue; }
+      // cosh / atan / asin read one argument of n entries, atan2 two (y, then x): the sweeps index both lists up to n
+      if (g.op >= OP_COSH && g.op <= OP_ASIN && (g.a0_len != g.n || g.a1_len != 0))
+        throw std::runtime_error("tape segment of opcode " + std::to_string(g.op) + " must have one argument of n entries");
+      if (g.op == OP_ATAN2 && (g.a0_len != g.n || g.a1_len != g.n))
+        throw std::runtime_error("tape segment of opcode 22 (atan2) must have two arguments of n entries each");
       i64 units = (g.op == 33) ? g.d0 * g.d2 : g.n;
       fs.push_back(fs.back() + units);
       h_flat_seg.push_back(s);

@@ -345,6 +345,19 @@ struct WaveIpm {
           hv[hb + n] = wi * u / (v * v);
           hv[hb + 2 * n] = -wi / v;
         }
+      } else if (op == OP_ATAN2) {
+        // atom_math.h atan2_rules (argument 0 is y); the stride of the three Hessian runs travels in u_p like rel_entr's
+        const Rule2x2 r = atan2_rules(at(ua0[e]), at(ua1[e]));
+        zz[zi] = r.val;
+        dv[ud0[e]] = r.gy;
+        dv[ud1[e]] = r.gx;
+        if (with_h) {
+          const double wi = ww[zi];
+          const i32 hb = uh[e], n = up[e];
+          hv[hb] = wi * r.hyy;
+          hv[hb + n] = -(wi * r.hyy);
+          hv[hb + 2 * n] = wi * r.hyx;
+        }
       } else {
         // OP_MATMUL: one output entry of U @ V (model.h sweep_flat)
         const i32 kk = ua1[e], db0 = ud0[e], db1 = ud1[e], hb = uh[e];

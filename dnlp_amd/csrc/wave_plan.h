@@ -60,7 +60,7 @@ inline const char* wave_plan_refusal(const Tape<E>& t, const SparsePlanHost* sp)
   if (t.nblk > 0 || t.ndense > 0) return "dense quad_form blocks";
   if (t.nred > 0) return "reduction-class segments (quad_form / quad_over_lin)";
   for (const SegHost& g : t.h_segs)
-    if (!(g.op < OP_MUL || g.op == OP_MUL || g.op == OP_REL_ENTR || g.op == OP_MATMUL)) return "an atom outside the elementwise / matmul set";
+    if (!(g.op < OP_MUL || g.op == OP_MUL || g.op == OP_REL_ENTR || g.op == OP_ATAN2 || g.op == OP_MATMUL)) return "an atom outside the elementwise / matmul set";
   if (sp->tail_n > 0 || sp->panels_dropped) return "plan with a dense tail";
   if (t.N + t.m > 4096 || t.nnzJ > 30000 || t.nnzH > 30000) return "too large for one wavefront";
   if (!t.jac_by_row.ptr || !t.jac_by_col.ptr || !t.hess_sym.ptr) return "no product index";
@@ -88,13 +88,13 @@ inline std::vector<i32> build_wave_plan(E* ex, const Tape<E>& t, const SparsePla
       const SegHost& g = t.h_segs[static_cast<size_t>(t.h_flat_seg[f])];
       if (g.op == OP_MATMUL) { gcount = std::max(gcount, std::max(g.a0_off + g.d0 * g.d1, g.a1_off + g.d1 * g.d2)); continue; }
       if (g.a0_base < 0) gcount = std::max(gcount, g.a0_off + g.n);
-      if ((g.op == OP_MUL || g.op == OP_REL_ENTR) && g.a1_base < 0) gcount = std::max(gcount, g.a1_off + g.n);
+      if ((g.op == OP_MUL || g.op == OP_REL_ENTR || g.op == OP_ATAN2) && g.a1_base < 0) gcount = std::max(gcount, g.a1_off + g.n);
     }
     const std::vector<i32> gidx = down32(t.gidx, gcount);
     std::vector<i32> op, a0, a1, z, d0, d1, hh, pp, mm;
     for (size_t f = 0; f < t.h_flat_seg.size(); ++f) {
       const SegHost& g = t.h_segs[static_cast<size_t>(t.h_flat_seg[f])];
-      const bool two = g.op == OP_MUL || g.op == OP_REL_ENTR;
+      const bool two = g.op == OP_MUL || g.op == OP_REL_ENTR || g.op == OP_ATAN2;
       if (g.op == OP_MATMUL) {
         // unit = output entry (r, c) of U (mm x kk) @ V (kk x pp), F-order (model.h sweep_flat): a0 = start of its kk index
         // pairs in mm_idx, a1 = kk, d0 / d1 = its dz/dU and dz/dV runs, h = its Hessian run
@@ -124,7 +124,7 @@ inline std::vector<i32> build_wave_plan(E* ex, const Tape<E>& t, const SparsePla
         d0.push_back(narrow(g.doff + i));
         d1.push_back(two ? narrow(g.doff + g.n + i) : -1);
         hh.push_back(narrow(g.hoff + i));
-        pp.push_back(g.op == OP_REL_ENTR ? narrow(g.n) : narrow(static_cast<i64>(f)));     // (rel_entr: the stride of its three Hessian runs)
+        pp.push_back(g.op == OP_REL_ENTR || g.op == OP_ATAN2 ? narrow(g.n) : narrow(static_cast<i64>(f)));     // (rel_entr, atan2: the stride of their three Hessian runs)
       }
     }
     h.mm_idx = put(mm);

@@ -121,6 +121,10 @@ ALIAS = {
     # no normcdf): the normal pair has no domain; loggamma's argument is always a new variable on [0, inf), like log's
     at.log_normcdf: (PLAIN,), at.normcdf: (PLAIN,),
     at.loggamma: (LOG_DOMAIN,),
+    # no reference rule (the reference has none of these atoms): cosh and atan have no domain, like sinh and asinh; asin's
+    # argument is always a new variable on [-1, 1], like atanh's
+    at.cosh: (PLAIN,), at.atan: (PLAIN,),
+    at.asin: (Aux(lower=-1, upper=1),),
 }
 
 
@@ -213,6 +217,13 @@ def _matrix_frac(atom, args):
         X = t
     T, row = _symmetrised(P)
     return atom.copy([X, T]), rows + [row]
+
+
+def _atan2(atom, args):
+    """No reference rule.  Both arguments aliased like _bilinear's, without its constant shortcut: a bare Variable stays,
+    anything else, a constant among them, becomes t == argument (as _matrix_frac's X), so both index lists of the tape
+    segment are x indices."""
+    return _alias_arguments(atom, args, (PLAIN, PLAIN))
 
 
 def _rel_entr(atom, args):
@@ -343,6 +354,7 @@ RULES.update({
     at.quad_over_lin: _quad_over_lin,
     at.QuadOverLinRows: _quad_over_lin_rows,
     at.rel_entr: _rel_entr,
+    at.atan2: _atan2,
     at.log_det: _log_det,
     at.MatrixFrac: _matrix_frac,
     # rewrites

@@ -44,7 +44,9 @@ from .expressions import Constant, Expression, Parameter, Variable
 OP_EXP, OP_LOG, OP_ENTR, OP_LOGISTIC, OP_POWER = 1, 2, 3, 4, 5
 OP_SIN, OP_COS, OP_TAN, OP_SINH, OP_TANH, OP_ASINH, OP_ATANH, OP_XEXP = 6, 7, 8, 9, 10, 11, 12, 13
 OP_LOG_NORMCDF, OP_NORMCDF, OP_LOGGAMMA = 14, 15, 16     # exact statistical atoms (csrc/atom_math.h), beyond the reference's set
+OP_COSH, OP_ATAN, OP_ASIN = 17, 18, 19                   # the partners of sinh / tan / sin, beyond the reference's set too
 OP_MUL, OP_REL_ENTR = 20, 21
+OP_ATAN2 = 22                # two arguments like OP_REL_ENTR: argument 0 is y, argument 1 is x
 OP_QUAD_FORM_DENSE, OP_QUAD_FORM_SPARSE, OP_QUAD_OVER_LIN, OP_MATMUL = 30, 31, 32, 33
 OP_LOG_SUM_EXP = 34          # row class: many short (or few long) reductions, one dense Hessian block per row
 OP_PROD = 35                 # row class: the same rows with the STRICT lower triangle (a product's Hessian diagonal is zero)
@@ -58,6 +60,7 @@ UNARY_OPS = {
     at.sin: OP_SIN, at.cos: OP_COS, at.tan: OP_TAN, at.sinh: OP_SINH, at.tanh: OP_TANH,
     at.asinh: OP_ASINH, at.atanh: OP_ATANH, at.xexp: OP_XEXP,
     at.log_normcdf: OP_LOG_NORMCDF, at.normcdf: OP_NORMCDF, at.loggamma: OP_LOGGAMMA,
+    at.cosh: OP_COSH, at.atan: OP_ATAN, at.asin: OP_ASIN,
 }
 
 # dense quad_form blocks up to this order are also listed in the COO Hessian pattern
@@ -660,6 +663,27 @@ class Lowerer:
             a1 = np.broadcast_to(a1.reshape(y.shape, order="F"), e.shape).reshape(-1, order="F")
         n = e.size
         seg = Segment(op=OP_REL_ENTR, n=n, a0=a0, a1=a1, zcount=n)
+        z = self.Z + np.arange(n)
+        self._new_segment(seg, np.concatenate([z, z]), np.concatenate([a0, a1]),
+                          np.concatenate([a0, a1, a0]), np.concatenate([a0, a1, a1]),
+                          np.concatenate([z, z, z]))
+        return self._z_form(seg.zoff, n)
+
+    def _lower_atan2(self, e):
+        """Layout of _lower_rel_entr: derivative runs y then x, Hessian runs (y, y), (x, x), (y, x)."""
+        y, x = e.args
+        a0 = self._gather(y)
+        a1 = self._gather(x)
+        if a0.size != e.size:
+            a0 = np.broadcast_to(a0.reshape(y.shape, order="F"), e.shape).reshape(-1, order="F")
+        if a1.size != e.size:
+            a1 = np.broadcast_to(a1.reshape(x.shape, order="F"), e.shape).reshape(-1, order="F")
+        if np.any(a0 == a1):
+            # the packed lower triangle would count the cross entry of a repeated index once instead of twice (as OP_MUL refuses a0 == a1)
+            raise ValueError("atan2 of a variable entry with itself is not supported (atan2(t, t) is the constant pi / 4 or "
+                             "-3 pi / 4 by the sign of t).")
+        n = e.size
+        seg = Segment(op=OP_ATAN2, n=n, a0=a0, a1=a1, zcount=n)
         z = self.Z + np.arange(n)
         self._new_segment(seg, np.concatenate([z, z]), np.concatenate([a0, a1]),
                           np.concatenate([a0, a1, a0]), np.concatenate([a0, a1, a1]),
