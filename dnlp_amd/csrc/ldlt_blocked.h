@@ -887,14 +887,19 @@ __global__ void __launch_bounds__(512, 4) gemm_nt_update_fast(double* __restrict
 
 // The same tiles with the pipelined body (PIPE) and, with `vec_ok & 4`, a grid of the lower tiles only (`lower` with
 // Nc <= M, diagonal at the block origin): blockIdx.x counts them column by column (csrc/lower_tile_map.h), so no
-// workgroup is launched to find out that it has nothing to do.  DNLP_LDLT_UPDATE_FORM selects (BlockedLdlt::init).
+// workgroup is launched to find out that it has nothing to do.  With `vec_ok & 8` the same grid walks the tiles in bands
+// of `band` tile rows (lower_tile_map_banded): a band's W rows are asked for again one tile column later, while they
+// are still in the Infinity Cache.  DNLP_LDLT_UPDATE_FORM selects (BlockedLdlt::init).
 template <int PIPE>
 __global__ void __launch_bounds__(512, 4) gemm_nt_update_fast_v(double* __restrict__ C, i64 ldc,
                                                                 const double* __restrict__ W, i64 ldw,
                                                                 const double* __restrict__ L, i64 ldl, int M,
-                                                                int Nc, int Kd, int lower, int ntm, int ntn, int vec_ok) {
+                                                                int Nc, int Kd, int lower, int ntm, int ntn, int vec_ok,
+                                                                int band) {
   int tm, tn;
-  if (vec_ok & 4) {
+  if (vec_ok & 8) {
+    lower_tile_map_banded(blockIdx.x, ntm, ntn, band, &tm, &tn);
+  } else if (vec_ok & 4) {
     lower_tile_map(blockIdx.x, ntm, ntn, &tm, &tn);
   } else {
     tm = blockIdx.x % ntm;
@@ -1840,8 +1845,15 @@ struct BlockedLdlt {
   bool padded = false;         // the matrix allocation has >= 128 doubles of slack behind it
   // Schur update kernel (DNLP_LDLT_UPDATE_FORM): bit 0 = software-pipelined operand reads (gemm_body_fast<.., 1>),
   // bit 1 = `lower` launches start only the tiles of the lower triangle; 0 = the single-register-set loop on the full
-  // ntm x ntn grid.  Every form gives the same bits.
-  int update_form = 3;
+  // ntm x ntn grid; bit 2 = the lower-triangle grid in bands of `update_band` tile rows (DNLP_LDLT_UPDATE_BAND) for
+  // launches taller than a band.  Every form gives the same bits.
+  int update_form = 7;
+  // Between two uses of a W line a banded launch moves band x (1 MB of W + 2 x 128 KB of C) + 1 MB of L (K = 1024):
+  // 121 MB at 96, 161 MB at 128, 201 MB at 160, against the 256 MiB of the Infinity Cache.  Measured on lone launches
+  // at M = 57 344 / 90 112 (profiles/update_band_ab.json): 64, 96 and 128 within 0.3 % of one another (+5 ... +6 % over
+  // the column order), 160 and 192 up to 1.5 % behind; 96 is the middle of the flat part and leaves half of the cache to
+  // the panel chain that runs beside the update.
+  int update_band = 96;
   int NB = 512;                // outer panel width (K of the MFMA Schur update)
   int small_tiles_below = 384; // launches with fewer 128 x 128 tiles than this use the 64 x 64 kernel (DNLP_LDLT_SMALL_TILES)
   int small_rows_max = 5120;   // ... and only up to this many rows: above, the launch runs beside a big update of the
@@ -1876,7 +1888,8 @@ struct BlockedLdlt {
     if (const char* ev = std::getenv("DNLP_LDLT_NB")) NB = std::atoi(ev);
     if (const char* ev = std::getenv("DNLP_LDLT_LOOKAHEAD")) lookahead = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("DNLP_LDLT_XCD")) xcd_swizzle = std::atoi(ev) != 0;
-    if (const char* ev = std::getenv("DNLP_LDLT_UPDATE_FORM")) update_form = std::atoi(ev) & 3;
+    if (const char* ev = std::getenv("DNLP_LDLT_UPDATE_FORM")) update_form = std::atoi(ev) & 7;
+    if (const char* ev = std::getenv("DNLP_LDLT_UPDATE_BAND")) update_band = std::max(1, std::atoi(ev));
     if (const char* ev = std::getenv("DNLP_LDLT_T128")) sub128 = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("DNLP_LDLT_FUSED_ROWS")) fused_rows = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("DNLP_LDLT_DIAG512")) diag512 = std::atoi(ev) != 0;
@@ -1955,13 +1968,15 @@ struct BlockedLdlt {
                          ldw, L, ldl, M, Nc, Kd, lower, ntm, vec_ok | 2);
     } else if (fast_ok && update_form != 0) {
       const bool tri = (update_form & 2) && lower && ntn <= ntm;
+      const bool banded = tri && (update_form & 4) && ntm > update_band;
+      const int order = vec_ok | (tri ? 4 : 0) | (banded ? 8 : 0);
       const unsigned grid = tri ? static_cast<unsigned>(lower_tile_count(ntm, ntn)) : static_cast<unsigned>(ntm) * ntn;
       if (update_form & 1)
         hipLaunchKernelGGL(gemm_nt_update_fast_v<1>, dim3(grid), dim3(512), 0, st, C, ld, W, ldw, L, ldl, M, Nc, Kd,
-                           lower, ntm, ntn, vec_ok | (tri ? 4 : 0));
+                           lower, ntm, ntn, order, update_band);
       else
         hipLaunchKernelGGL(gemm_nt_update_fast_v<0>, dim3(grid), dim3(512), 0, st, C, ld, W, ldw, L, ldl, M, Nc, Kd,
-                           lower, ntm, ntn, vec_ok | (tri ? 4 : 0));
+                           lower, ntm, ntn, order, update_band);
     } else if (fast_ok)
       hipLaunchKernelGGL(gemm_nt_update_fast, dim3(static_cast<unsigned>(ntm) * ntn), dim3(512), 0, st, C, ld, W,
                          ldw, L, ldl, M, Nc, Kd, lower, ntm, vec_ok);

@@ -3,7 +3,10 @@
 // (default 3: pipelined operand reads on the lower-triangle grid) on identical copies of C, the two results compared
 // bit for bit (on the device: at M = 90 112 a copy of C is 65 GB), then 5 timed launches of each after 2 warm-ups, the
 // forms alternating.  One JSON line.  `update_ab M K form` runs that one form alone (one kernel for a counter pass).
-// UPDATE_AB_FORM / UPDATE_AB_BASE choose the two forms of the A/B (default 3 against 0), e.g. each lever on its own.
+// UPDATE_AB_FORM / UPDATE_AB_BASE choose the two forms of the A/B (default 3 against 0), e.g. each lever on its own;
+// UPDATE_AB_BAND the band height of the banded forms (4-7) in tiles.  `update_ab M K form LD [LDW]` (form -1: the A/B)
+// gives C and L the leading dimension LD >= M and W the leading dimension LDW (default LD), so that a lone launch runs
+// at the column stride of a trailing block inside a larger matrix (n = 1e5: LD 100 008, LDW 100 000), not at M.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -I dnlp_amd/csrc tools/micro/update_ab.hip -o tools/micro/bin/update_ab -lhiprtc
 #include "ldlt_blocked.h"
 #include <cstdio>
@@ -41,31 +44,35 @@ __global__ void ab_diff(const unsigned long long* a, const unsigned long long* b
 }
 
 int main(int argc, char** argv) {
-  if (argc < 3) { fprintf(stderr, "usage: update_ab M K [form]\n"); return 2; }
+  if (argc < 3) { fprintf(stderr, "usage: update_ab M K [form [LD [LDW]]]\n"); return 2; }
   const int M = atoi(argv[1]), K = atoi(argv[2]);
   const int single = argc > 3 ? atoi(argv[3]) : -1;
   const int other = std::getenv("UPDATE_AB_FORM") ? atoi(std::getenv("UPDATE_AB_FORM")) : 3;   // the form set against ...
   const int base = std::getenv("UPDATE_AB_BASE") ? atoi(std::getenv("UPDATE_AB_BASE")) : 0;     // ... this one (0: the parent's)
+  const int LD = argc > 4 ? atoi(argv[4]) : M, LDW = argc > 5 ? atoi(argv[5]) : LD;
+  const int band = std::getenv("UPDATE_AB_BAND") ? atoi(std::getenv("UPDATE_AB_BAND")) : 0;    // 0: BlockedLdlt's default
   if (M <= 0 || M % 8 || K <= 0 || K % GM_BK) { fprintf(stderr, "M: a multiple of 8, K: a multiple of %d\n", GM_BK); return 2; }
-  const size_t nC = static_cast<size_t>(M) * M, nW = static_cast<size_t>(M) * K, slack = 256;
+  if (LD < M || LD % 8 || LDW < M || LDW % 8) { fprintf(stderr, "LD, LDW: multiples of 8, at least M\n"); return 2; }
+  const size_t nC = static_cast<size_t>(LD) * M, nL = static_cast<size_t>(LD) * K, nW = static_cast<size_t>(LDW) * K, slack = 256;
   double *W, *L, *Cs[2] = {nullptr, nullptr};
   unsigned long long* ndiff;
   CK(hipMalloc(&W, (nW + slack) * 8));
-  CK(hipMalloc(&L, (nW + slack) * 8));
+  CK(hipMalloc(&L, (nL + slack) * 8));
   CK(hipMalloc(&ndiff, 8));
   const int ncopies = single >= 0 ? 1 : 2;
   for (int c = 0; c < ncopies; ++c) CK(hipMalloc(&Cs[c], (nC + slack) * 8));
   hipLaunchKernelGGL(ab_fill, dim3(4096), dim3(256), 0, 0, W, nW + slack, 11ull);
-  hipLaunchKernelGGL(ab_fill, dim3(4096), dim3(256), 0, 0, L, nW + slack, 12ull);
+  hipLaunchKernelGGL(ab_fill, dim3(4096), dim3(256), 0, 0, L, nL + slack, 12ull);
   for (int c = 0; c < ncopies; ++c) hipLaunchKernelGGL(ab_fill, dim3(8192), dim3(256), 0, 0, Cs[c], nC + slack, 13ull);
   CK(hipMemset(ndiff, 0, 8));
   CK(hipDeviceSynchronize());
 
   BlockedLdlt bl;                 // only what gemm() reads: no workspace, no streams
-  bl.ld = M; bl.ldw = M; bl.padded = true; bl.small_tiles_below = 0;
+  bl.ld = LD; bl.ldw = LDW; bl.padded = true; bl.small_tiles_below = 0;
+  if (band > 0) bl.update_band = band;
   auto run = [&](int form, double* C) {
     bl.update_form = form;
-    bl.gemm(nullptr, C, W, L, M, M, M, K, 1);
+    bl.gemm(nullptr, C, W, L, LD, M, M, K, 1);
   };
   const double flops = 2.0 * K * (static_cast<double>(M) * (M + 1) / 2);
   hipEvent_t e0, e1;
@@ -82,8 +89,8 @@ int main(int argc, char** argv) {
       CK(hipEventElapsedTime(&t, e0, e1));
       if (r) ms += t / 2;
     }
-    printf("{\"tool\": \"update_ab\", \"M\": %d, \"K\": %d, \"form\": %d, \"launches\": 3, \"ms\": %.4f, \"TF\": %.3f}\n", M, K,
-           single, ms, flops / (ms * 1e-3) * 1e-12);
+    printf("{\"tool\": \"update_ab\", \"M\": %d, \"K\": %d, \"LD\": %d, \"LDW\": %d, \"band\": %d, \"form\": %d, \"launches\": 3, "
+           "\"ms\": %.4f, \"TF\": %.3f}\n", M, K, LD, LDW, bl.update_band, single, ms, flops / (ms * 1e-3) * 1e-12);
     return 0;
   }
   const int forms[2] = {base, other};
@@ -108,10 +115,11 @@ int main(int argc, char** argv) {
                      reinterpret_cast<const unsigned long long*>(Cs[1]), nC + slack, ndiff);
   unsigned long long nd2 = 0;
   CK(hipMemcpy(&nd2, ndiff, 8, hipMemcpyDeviceToHost));
-  printf("{\"tool\": \"update_ab\", \"M\": %d, \"K\": %d, \"forms\": [%d, %d], \"ms\": [%.4f, %.4f], \"ms_min\": [%.4f, %.4f], "
+  printf("{\"tool\": \"update_ab\", \"M\": %d, \"K\": %d, \"LD\": %d, \"LDW\": %d, \"band\": %d, \"forms\": [%d, %d], "
+         "\"ms\": [%.4f, %.4f], \"ms_min\": [%.4f, %.4f], "
          "\"TF\": [%.3f, %.3f], \"speedup\": %.4f, \"words_differing_first_launch\": %llu, \"words_differing_after_8\": %llu, "
          "\"bits_equal\": %s}\n",
-         M, K, base, other, ms[0], ms[1], best[0], best[1], flops / (ms[0] * 1e-3) * 1e-12, flops / (ms[1] * 1e-3) * 1e-12,
+         M, K, LD, LDW, bl.update_band, base, other, ms[0], ms[1], best[0], best[1], flops / (ms[0] * 1e-3) * 1e-12, flops / (ms[1] * 1e-3) * 1e-12,
          ms[0] / ms[1], nd, nd2, (nd == 0 && nd2 == 0) ? "true" : "false");
   return (nd == 0 && nd2 == 0) ? 0 : 1;
 }
